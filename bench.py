@@ -1,8 +1,18 @@
 """Headline benchmark: Llama-3-8B NF4 (double quant) batch-1 greedy decode on MI355X
-(BASELINE.json configs[1]) plus the 4096x4096 decode-GEMV roofline and the
-config #1 CPU dequant+matmul baseline.
+(BASELINE.json configs[1]); with --full also the 4096x4096 decode-GEMV roofline and
+the config #1 CPU dequant+matmul baseline.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+* A plain run builds the model, warms up, times the K decode steps and prints the
+  result line (value, ms_per_step, config); nothing else is measured.  --full adds
+  every other measurement described below (the second code table's decode, the
+  weak-scaling extra, roofline, parity, chain_roofline, rowsplit_layer, prefill,
+  cpu_baseline) to the same line; the --no-* switches drop single ones of them.
+* --dump-outputs DIR: after the timed steps, what the last timed step computed is
+  written as DIR/logits.npy (float32 [batch, vocab], the step's logits) and
+  DIR/tokens.npy (float64, the greedy token history the step appended to).  Model
+  weights and prompt are seeded, so two builds can be compared output for output.
 
 * Model: transformers LlamaForCausalLM with the Llama-3-8B architecture,
   random-init fp16 weights (no network -> no checkpoint), every decoder
@@ -19,13 +29,13 @@ config #1 CPU dequant+matmul baseline.
   scaling, global batch 1, parallelism tp{N}-rowsplit-allgather.  The
   weak-scaling layout (--weak: one bs=1 stream per GPU, global batch N,
   Megatron pairing -- q/k/v/gate/up column-parallel, o/down row-parallel +
-  one all-reduce each) is measured after it and reported only as the extra
-  key `weak_scaling_extra` (--no-extra-weak skips it).
-* roofline: the 4096x4096 NF4+DQ fused GEMV alone, 64 rotating weight copies
+  one all-reduce each) is measured after it by --full and reported only as the
+  extra key `weak_scaling_extra` (--no-extra-weak skips it).
+* roofline (--full): the 4096x4096 NF4+DQ fused GEMV alone, 64 rotating weight copies
   (> the 256 MiB Infinity Cache), HIP events on the launch stream around 400
   back-to-back launches (average launch duration, matches rocprofv3);
   algorithmic bytes per launch = 8,672,324.
-* cpu_baseline (rank 0, N = 1): the oracle's CPU dequant + torch.matmul of one
+* cpu_baseline (--full, rank 0, N = 1): the oracle's CPU dequant + torch.matmul of one
   Linear4bit(4096,4096) NF4 layer (config #1), scaled to the 224 Linear4bit
   layers of one token.
 """
@@ -87,7 +97,10 @@ def build_model(layers: int, seed: int, model_name: str = "llama3-8b", quant_typ
 
 
 @torch.inference_mode()
-def decode_bench(model, cfg, steps: int, warmup: int, prompt_len: int, world: int, batch: int = 1):
+def decode_bench(model, cfg, steps: int, warmup: int, prompt_len: int, world: int, batch: int = 1,
+                 outputs: dict | None = None):
+    """`outputs`, when a dict, receives the last timed step's "logits" ([batch, vocab] fp32)
+    and the timed steps' "tokens"."""
     from transformers.cache_utils import DynamicCache
 
     dev = torch.device("cuda")
@@ -112,6 +125,9 @@ def decode_bench(model, cfg, steps: int, warmup: int, prompt_len: int, world: in
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if outputs is not None:
+        outputs["logits"] = out.logits[:, -1].float()
+        outputs["tokens"] = torch.cat(toks, dim=1)
     return dt, torch.cat(toks, dim=1)
 
 
@@ -134,14 +150,15 @@ def greedy_token(logits: torch.Tensor) -> torch.Tensor:
 
 @torch.inference_mode()
 def decode_bench_graph(model, cfg, steps: int, warmup: int, prompt_len: int, world: int, batch: int = 1,
-                       graph: bool = True, device: str = "cuda"):
+                       graph: bool = True, device: str = "cuda", outputs: dict | None = None):
     """Same workload as decode_bench, with the decode step captured once into a HIP
     graph (StaticCache, static token/position buffers; the graph contains the
     whole forward, the argmax and the feedback of the token into the next
     step).  One replay = one generated token per stream (`batch` streams).
     graph=False runs the identical step eagerly (the gloo CPU test of the
     multi-GPU layout drives this function with it).  Returns (seconds for the
-    timed steps, token history [batch, prompt + warmup + steps + 8])."""
+    timed steps, token history [batch, prompt + warmup + steps + 8]).  `outputs`, when a dict,
+    receives the last timed step's "logits" ([batch, vocab] fp32) and the history as "tokens"."""
     from transformers.cache_utils import StaticCache
 
     dev = torch.device(device)
@@ -159,6 +176,8 @@ def decode_bench_graph(model, cfg, steps: int, warmup: int, prompt_len: int, wor
     def step():
         lo = model(input_ids=tok, past_key_values=cache, cache_position=pos, position_ids=pos_ids,
                    use_cache=True).logits
+        if outputs is not None:
+            outputs["logits"] = lo[:, -1]   # under capture: the graph's own buffer, rewritten by every replay
         if GREEDY == "kernel" and lo.is_cuda:
             from quantizations_amd.layer_ops import greedy_step
             greedy_step(lo[:, -1], hist, pos, tok)   # argmax + the three feedback writes, one launch
@@ -196,7 +215,30 @@ def decode_bench_graph(model, cfg, steps: int, warmup: int, prompt_len: int, wor
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if outputs is not None:
+        outputs["logits"] = outputs["logits"].float()
+        outputs["tokens"] = hist
     return dt, hist
+
+
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: all arrays together
+
+
+def dump_outputs(dirpath: str, outputs: dict) -> None:
+    """--dump-outputs: each tensor of `outputs` as DIR/<name>.npy, floating point as float32 and
+    integers as float64 (exact for token ids).  An array larger than its share of the 64 MB
+    budget is written as a fixed, seeded sample of its flattened elements."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(outputs))
+    for name, t in sorted(outputs.items()):
+        t = t.detach().cpu()
+        a = t.to(torch.float32 if t.is_floating_point() else torch.float64).numpy()
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def prepare_decode_model(model, rank: int, world: int, sharded: bool, tp_mode: str = "gather",
@@ -1101,6 +1143,11 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--prompt", type=int, default=32)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed decode also run every other measurement of the line (other code table, "
+                         "weak-scaling extra, roofline, parity, chain, row-split layer, prefill, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's logits and the greedy token history as DIR/<name>.npy")
     ap.add_argument("--layers", type=int, default=0, help="decoder layers (0 = the model's own count)")
     ap.add_argument("--model", choices=sorted(MODELS), default="llama3-8b",
                     help="llama3-8b (configs #1-#4) or llama3-70b (config #5)")
@@ -1190,6 +1237,8 @@ def main():
         ap.error("--weak and --strong are exclusive")
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the N ranks here, before
@@ -1243,7 +1292,8 @@ def main():
     global GREEDY
     GREEDY = "torch" if args.torch_argmax else args.greedy
 
-    def run_decode(tp_mode: str, gbatch: int, steps: int, warmup: int, cdt: torch.dtype = compute_dtype):
+    def run_decode(tp_mode: str, gbatch: int, steps: int, warmup: int, cdt: torch.dtype = compute_dtype,
+                   outputs: dict | None = None):
         t_build = time.perf_counter()
         model, cfg = build_model(args.layers, seed=0, model_name=args.model, quant_type=args.quant,
                                  double_quant=not args.no_dq,
@@ -1264,13 +1314,13 @@ def main():
         mode = "eager"
         if not args.eager:
             try:
-                dt, _ = decode_bench_graph(model, cfg, steps, warmup, args.prompt, world, gbatch)
+                dt, _ = decode_bench_graph(model, cfg, steps, warmup, args.prompt, world, gbatch, outputs=outputs)
                 mode = "hipgraph"
             except Exception as e:  # capture unsupported by this transformers build -> eager
                 log(f"[rank {rank}] graph decode failed ({type(e).__name__}: {e}); falling back to eager")
                 torch.cuda.synchronize()
         if mode == "eager":
-            dt, _ = decode_bench(model, cfg, steps, warmup, args.prompt, world, gbatch)
+            dt, _ = decode_bench(model, cfg, steps, warmup, args.prompt, world, gbatch, outputs=outputs)
         t = torch.tensor([dt], device="cuda")
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)   # the slowest rank's time
@@ -1284,11 +1334,14 @@ def main():
         return parallelism_name(tp_mode, world, sharded)
 
     weak, tp_mode, gbatch = decode_layout(args, world, sharded)
-    dt, mode, cfg, n_groups, n_layer_ops = run_decode(tp_mode, gbatch, args.steps, args.warmup)
+    outputs = {} if args.dump_outputs else None
+    dt, mode, cfg, n_groups, n_layer_ops = run_decode(tp_mode, gbatch, args.steps, args.warmup, outputs=outputs)
     tok_s = args.steps * gbatch / dt   # tokens generated by all streams, whole job
+    if outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
 
     extra_weak = None
-    if world > 1 and not weak and not args.no_extra_weak:
+    if args.full and world > 1 and not weak and not args.no_extra_weak:
         # the weak-scaling layout, reported beside the headline only (extra key)
         w_steps = max(8, args.steps // 2)
         wdt, wmode, _, _, _ = run_decode("pair", args.batch * world, w_steps, args.warmup)
@@ -1297,7 +1350,8 @@ def main():
                       "global_batch": args.batch * world, "decode": wmode, "parallelism": parallelism("pair")}
 
     extra_codes = None
-    if world == 1 and not sharded and not args.no_extra_codes and args.dtype == "fp16" and args.quant == "nf4":
+    if (args.full and world == 1 and not sharded and not args.no_extra_codes and args.dtype == "fp16"
+            and args.quant == "nf4"):
         # the same decode with the other fp16-activation code table (reported beside the headline)
         other = torch.float16 if compute_dtype == torch.float32 else torch.float32
         c_steps = max(16, args.steps // 2)
@@ -1311,13 +1365,13 @@ def main():
     roof = None
     parity = None
     chain = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         roof = _safe(roofline_object, args, layer_ops)
         parity = _safe(gemv_parity)
         chain = _safe(chain_roofline)
 
     layer = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         layer = rowsplit_layer(rank, world, sharded, gatherer=gatherer)   # every rank takes part (the all-gather)
     if gatherer is not None and gatherer.failed_anywhere():
         # a one-shot exchange gave up waiting for a peer (5 s bound): its outputs, and so the
@@ -1328,11 +1382,11 @@ def main():
         sys.exit(4)
 
     prefill = None
-    if rank == 0 and world == 1 and not args.no_prefill:
+    if args.full and rank == 0 and world == 1 and not args.no_prefill:
         prefill = prefill_bench()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline()
 
     if rank == 0:
@@ -1357,6 +1411,7 @@ def main():
                        "parallelism": parallelism(tp_mode),
                        "projection_groups": n_groups, "layer_ops": n_layer_ops},
             "roofline": roof, "parity": parity, "cpu_baseline": cpu, "prefill_config4": prefill,
+            "full": bool(args.full),   # False: the extra measurements were not run (their keys are null or absent)
         }
         line["config"]["compute_dtype"] = args.compute_dtype
         line["config"]["rmsnorm_in_grouped_gemv"] = bool(not args.no_prenorm and not args.no_fuse

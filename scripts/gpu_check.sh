@@ -5,7 +5,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 PYTEST_ARGS=${PYTEST_ARGS:-"tests -m gpu -q --maxfail=40"}
-BENCH_ARGS=${BENCH_ARGS:-"--steps 16 --warmup 4"}
+BENCH_ARGS=${BENCH_ARGS:-"--full --steps 16 --warmup 4"}
 step() {  # name timeout cmd...
   local name=$1 to=$2; shift 2
   timeout -k 10 "$to" "$@" > "gpurun_out/$name.log" 2>&1

@@ -366,6 +366,44 @@ int qz_gemv_4bit_pair_silu(const qz_gemv_segment *segs, int K, const void *x, in
                            int blocksize, int blocksize2, const float *lut, const void *norm_weight, float eps,
                            void *h, void *stream);
 
+/* LoRA adapters on the decode GEMVs (extension; the peft form base(x) + lora_B(lora_A(x)) * scaling
+ * for one token of F16/BF16 activations, adapter tensors in the activation dtype, rank 1..64):
+ *   t[j] = scaling * sum_k A[j,k] * x'[k]                      fp32 (qz_lora_shrink)
+ *   y[m] = round((W x')[m] (+ bias[m]) + sum_j B[m,j] * t[j])   (the *_lora GEMVs; fp32 accumulation)
+ * A is [r, K] and B is [M, r], row-major.  scaling is ONE fp32 value in device memory, read by the
+ * shrink launch only (a captured graph does not bake it in). */
+#define QZ_LORA_MAX_RANK 64
+typedef struct qz_lora_shrink_segment {
+  const void *A;        /* [r, K], the dtype of x, 16-B aligned */
+  const float *scaling; /* device, one value */
+  int r;
+  int t_offset;         /* this adapter's t is t[t_offset .. t_offset + r) */
+} qz_lora_shrink_segment;
+/* t for 1..QZ_GEMV_MAX_SEGMENTS adapters that read the same x, in one launch.  norm_weight
+ * (nullable): x' = norm_weight * rmsnorm(x, eps) as qz_rmsnorm stores it (the bits the fused-norm
+ * GEMV multiplies); else x' = x.  K % 8 == 0 and 16-B-aligned x, A and norm_weight, else
+ * QZ_ERR_SHAPE (nothing launched). */
+int qz_lora_shrink(int nseg, const qz_lora_shrink_segment *segs, int K, const void *x, int dtype,
+                   const void *norm_weight, float eps, float *t, void *stream);
+/* qz_gemv_4bit / qz_gemv_4bit_residual (residual nullable) with the adapter term added to the fp32
+ * row sums before the output rounding: lora_B [M, r] of `dtype`, t fp32[r] from qz_lora_shrink. */
+int qz_gemv_4bit_lora(int M, int K, const void *x, int dtype, const unsigned char *B, int quant_type, int blocksize,
+                      const float *absmax, const unsigned char *qabsmax, const float *absmax2, const float *code2,
+                      const float *offset, int blocksize2, long long block_base, const float *lut, const void *bias,
+                      const void *residual, const void *lora_B, int r, const float *t, void *y, void *stream);
+/* qz_gemv_4bit_grouped (norm_weight NULL) / qz_gemv_4bit_grouped_rmsnorm with one adapter operand
+ * per segment, parallel to segs: B == NULL = that segment has no adapter (its output is the plain
+ * launch's, bit for bit); else its t is t[t_offset .. t_offset + r).  Declines (QZ_ERR_SHAPE) what
+ * qz_gemv_4bit_grouped_rmsnorm declines. */
+typedef struct qz_lora_segment {
+  const void *B; /* [M, r] of the activation dtype, or NULL */
+  int r;
+  int t_offset;
+} qz_lora_segment;
+int qz_gemv_4bit_grouped_lora(int nseg, const qz_gemv_segment *segs, const qz_lora_segment *lora, const float *t,
+                              int K, const void *x, int dtype, int quant_type, int blocksize, int blocksize2,
+                              const float *lut, const void *norm_weight, float eps, void *stream);
+
 /* The launch-geometry measurement knobs in effect (QZ_GEMV_WIDE8, QZ_GROUPED_NORM_R, QZ_PAIR_R,
  * QZ_PAIR_WT, QZ_PAIR_PS, QZ_PAIR_WK1, and QZ_GEMM16_SCHED -- the schedule qz_gemm_16bit (default 971, persistent)
  * launches: environment variables read ONCE when the library is loaded) and the

@@ -43,6 +43,19 @@ class GemvSegment(ctypes.Structure):
                 ("y", ctypes.c_void_p)]
 
 
+class LoraSegment(ctypes.Structure):
+    """struct qz_lora_segment (include/quantizations.h)."""
+    _fields_ = [("B", ctypes.c_void_p), ("r", ctypes.c_int), ("t_offset", ctypes.c_int)]
+
+
+class LoraShrinkSegment(ctypes.Structure):
+    """struct qz_lora_shrink_segment (include/quantizations.h)."""
+    _fields_ = [("A", ctypes.c_void_p), ("scaling", ctypes.c_void_p), ("r", ctypes.c_int),
+                ("t_offset", ctypes.c_int)]
+
+
+LORA_MAX_RANK = 64  # QZ_LORA_MAX_RANK
+
 # name -> argtypes (restype int unless noted); mirrors include/quantizations.h
 SIGNATURES = {
     "cgemm_4bit_inference_naive_fp32": [_i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i],
@@ -60,6 +73,9 @@ SIGNATURES = {
     "qz_gemv_4bit_grouped": [_i, _p, _i, _p, _i, _i, _i, _i, _p, _p],
     "qz_gemv_4bit_grouped_rmsnorm": [_i, _p, _i, _p, _i, _i, _i, _i, _p, _p, _f, _p],
     "qz_gemv_4bit_pair_silu": [_p, _i, _p, _i, _i, _i, _i, _p, _p, _f, _p, _p],
+    "qz_lora_shrink": [_i, _p, _i, _p, _i, _p, _f, _p, _p],
+    "qz_gemv_4bit_lora": [_i, _i, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _ll, _p, _p, _p, _p, _i, _p, _p, _p],
+    "qz_gemv_4bit_grouped_lora": [_i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _p, _p, _f, _p],
     "qz_decode_attention": [_i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p, _ll, _ll,
                             _p, _p, _p, _ll, _p, _f, _p],
     "qz_gemm_4bit": [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _ll, _p],

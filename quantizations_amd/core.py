@@ -410,14 +410,16 @@ def exact_codes_for(compute_dtype):
 
 def gemv_4bit(A: Tensor, B: Tensor, out: Optional[Tensor] = None, transposed_A=False, transposed_B=False,
               state=None, bias: Optional[Tensor] = None, block_base: int = 0,
-              exact_codes: Optional[bool] = None, residual: Optional[Tensor] = None) -> Tensor:
+              exact_codes: Optional[bool] = None, residual: Optional[Tensor] = None, lora=None) -> Tensor:
     """Batch-1 4-bit GEMV (reference core.py:426-504) as ONE fused kernel:
     y = x . W^T (+ bias), W from `state`; out dtype = A.dtype.  fp32 activations are
     multiplied by the fp32 codebook values and bf16 ones by bf16 hi + lo codes; for fp16
     activations `exact_codes` (default GEMV_EXACT_CODES) picks the exact hi + lo fp16 codes
     over the fp16-rounded ones.  `residual` (a contiguous A.dtype tensor of M elements;
     not in the reference): returns residual + y with the add in the kernel's epilogue
-    (qz_gemv_4bit_residual, bit-identical to the torch add)."""
+    (qz_gemv_4bit_residual, bit-identical to the torch add).  `lora` = (lora_B [M, r] of
+    A.dtype, t fp32 [r] from lora.shrink): the adapter term B . t is added to the fp32 row sums
+    in the same launch (qz_gemv_4bit_lora; 16-bit A only)."""
     if state is None:
         raise ValueError("state cannot None. gem_4bit( ) requires the state from quantize_4bit( )")
     if A.numel() != A.shape[-1]:
@@ -432,10 +434,20 @@ def gemv_4bit(A: Tensor, B: Tensor, out: Optional[Tensor] = None, transposed_A=F
     A = A.contiguous()
     if bias is not None and bias.dtype != A.dtype:
         bias = bias.to(A.dtype)
+    if residual is not None and (residual.dtype != A.dtype or residual.numel() != M or not residual.is_contiguous()
+                                 or residual.device != A.device):
+        raise ValueError(f"gemv_4bit: residual must be a contiguous {A.dtype} tensor of {M} elements")
+    if lora is not None:
+        lB, t = lora
+        if lB.dtype != A.dtype or lB.dim() != 2 or lB.shape[0] != M or not lB.is_contiguous() or \
+                t.dtype != torch.float32 or t.numel() != lB.shape[1] or not t.is_contiguous():
+            raise ValueError(f"gemv_4bit: lora must be (B [{M}, r] contiguous {A.dtype}, t fp32 [r])")
+        check(lib.qz_gemv_4bit_lora(M, K, ptr(A), dtype_code(A.dtype), ptr(B),
+                                    _gemv_quant_type(state.quant_type, exact_codes, A.dtype), state.blocksize,
+                                    *state.scale_args(), block_base, 0, ptr(bias), ptr(residual), ptr(lB),
+                                    int(lB.shape[1]), ptr(t), ptr(out), _lib.stream_of(A)), "gemv_4bit(lora)")
+        return out
     if residual is not None:
-        if residual.dtype != A.dtype or residual.numel() != M or not residual.is_contiguous() \
-                or residual.device != A.device:
-            raise ValueError(f"gemv_4bit: residual must be a contiguous {A.dtype} tensor of {M} elements")
         check(lib.qz_gemv_4bit_residual(M, K, ptr(A), dtype_code(A.dtype), ptr(B),
                                         _gemv_quant_type(state.quant_type, exact_codes, A.dtype), state.blocksize,
                                         *state.scale_args(), block_base, 0, ptr(bias), ptr(residual), ptr(out),
@@ -501,7 +513,7 @@ def gemv_4bit_pair_silu(A: Tensor, items, exact_codes: Optional[bool] = None, no
     return h
 
 
-def gemv_4bit_grouped(A: Tensor, items, exact_codes: Optional[bool] = None, norm=None) -> list:
+def gemv_4bit_grouped(A: Tensor, items, exact_codes: Optional[bool] = None, norm=None, lora=None) -> list:
     """Several batch-1 4-bit GEMVs that share the input vector A, in ONE launch
     (qz_gemv_4bit_grouped).  items: sequence of
     (B, state, bias[, block_base[, out]]) with equal K, quant_type, blocksize
@@ -512,7 +524,11 @@ def gemv_4bit_grouped(A: Tensor, items, exact_codes: Optional[bool] = None, norm
     norm=(weight, eps): A is the INPUT of a Llama RMSNorm and every GEMV takes
     layer_ops.rms_norm(A, weight, eps) -- computed inside the same launch
     (qz_gemv_4bit_grouped_rmsnorm, bit-identical to the separate norm) where the
-    kernel takes the shape, else as two launches."""
+    kernel takes the shape, else as two launches.
+
+    lora=(t, [None | (lora_B_i, t_offset_i)]): segment i adds lora_B_i [M_i, r_i] . t[t_offset_i :
+    t_offset_i + r_i] to its fp32 row sums (qz_gemv_4bit_grouped_lora; 16-bit A only); t is
+    lora.shrink's output for the same A and norm."""
     items = list(items)
     if not 1 <= len(items) <= _lib.GEMV_MAX_SEGMENTS:
         raise ValueError(f"gemv_4bit_grouped takes 1..{_lib.GEMV_MAX_SEGMENTS} weights, got {len(items)}")
@@ -546,11 +562,37 @@ def gemv_4bit_grouped(A: Tensor, items, exact_codes: Optional[bool] = None, norm
     bs2 = int(s0.state2.blocksize) if s0.nested else 0
     qt = _gemv_quant_type(s0.quant_type, exact_codes, A.dtype)
     segp = ctypes.cast(segs, ctypes.c_void_p)
+    lsegp = None
+    if lora is not None:
+        t, entries = lora
+        if len(entries) != len(items) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("gemv_4bit_grouped: lora must be (t fp32, one entry per weight)")
+        lsegs = (_lib.LoraSegment * len(items))()
+        for i, ent in enumerate(entries):
+            if ent is None:
+                lsegs[i] = _lib.LoraSegment(None, 0, 0)
+                continue
+            lB, off = ent
+            if lB.dtype != A.dtype or lB.dim() != 2 or lB.shape[0] != items[i][1].shape[0] or \
+                    not lB.is_contiguous() or off < 0 or off + lB.shape[1] > t.numel():
+                raise ValueError(f"gemv_4bit_grouped: lora entry {i} must be (B [M, r] contiguous {A.dtype}, t_offset)")
+            lsegs[i] = _lib.LoraSegment(ptr(lB), int(lB.shape[1]), int(off))
+        lsegp = ctypes.cast(lsegs, ctypes.c_void_p)
+
+    def launch(x, nw, eps):
+        if lsegp is None:
+            if nw is None:
+                return lib.qz_gemv_4bit_grouped(len(items), segp, K, ptr(x), dtype_code(x.dtype), qt, s0.blocksize,
+                                                bs2, 0, _lib.stream_of(x))
+            return lib.qz_gemv_4bit_grouped_rmsnorm(len(items), segp, K, ptr(x), dtype_code(x.dtype), qt,
+                                                    s0.blocksize, bs2, 0, ptr(nw), float(eps), _lib.stream_of(x))
+        return lib.qz_gemv_4bit_grouped_lora(len(items), segp, lsegp, ptr(lora[0]), K, ptr(x), dtype_code(x.dtype), qt,
+                                             s0.blocksize, bs2, 0, ptr(nw), float(eps), _lib.stream_of(x))
+
     if norm is not None:
         nw, eps = norm
         if nw.dtype == A.dtype and nw.is_cuda and nw.is_contiguous() and nw.numel() == K:
-            rc = lib.qz_gemv_4bit_grouped_rmsnorm(len(items), segp, K, ptr(A), dtype_code(A.dtype), qt, s0.blocksize,
-                                                  bs2, 0, ptr(nw), float(eps), _lib.stream_of(A))
+            rc = launch(A, nw, eps)
             if rc != _lib.QZ_ERR_SHAPE:
                 check(rc, "gemv_4bit_grouped(norm)")
                 LAST_FORM["grouped"] = "grouped (norm fused)"
@@ -558,9 +600,7 @@ def gemv_4bit_grouped(A: Tensor, items, exact_codes: Optional[bool] = None, norm
         from .layer_ops import rms_norm
         A = rms_norm(A, nw, eps).contiguous()   # shapes the fused launch does not take: two launches
     LAST_FORM["grouped"] = "grouped" if norm is None else "norm launch + grouped"
-    check(lib.qz_gemv_4bit_grouped(len(items), segp, K, ptr(A), dtype_code(A.dtype), qt, s0.blocksize, bs2, 0,
-                                   _lib.stream_of(A)),
-          "gemv_4bit_grouped")
+    check(launch(A, None, 0.0), "gemv_4bit_grouped")
     return outs
 
 

@@ -96,38 +96,10 @@ __global__ __launch_bounds__(256) void k_gemv_4bit_pair(GemvGroup g) {
   gemv_body<DQ, DT, R, 1, 4, true, CL, WT, NRM, true, TWO, PS>(seg, blockIdx.x, g.seg);
 }
 
-// Generic path for shapes the vector kernel does not cover (K % 32 != 0,
-// odd K, blocksize < 32): one wave per row, flat element addressing exactly
-// as the reference (e = r*K + k, byte e>>1, high nibble for even e).
+// Generic path for shapes the vector kernel does not cover (gemv_core.h gemv_generic_body)
 template <bool DQ, int DT>
 __global__ __launch_bounds__(256) void k_gemv_4bit_generic(GemvParams p, int quant_type) {
-  __shared__ float s_lut[16];
-  if (threadIdx.x < 16) s_lut[threadIdx.x] = p.lut ? p.lut[threadIdx.x] : 0.0f;
-  __syncthreads();
-  const int lane = threadIdx.x & (kWave - 1);
-  const int row = blockIdx.x * 4 + threadIdx.x / kWave;
-  if (row >= p.M) return;
-  const float offset = DQ ? *p.sc.offset : 0.0f;
-  float acc = 0.0f;
-  for (int k = lane; k < p.K; k += kWave) {
-    const long long e = (long long)row * p.K + k;
-    const uint32_t byte = p.B[e >> 1];
-    const uint32_t nib = (e & 1) ? (byte & 0xFu) : (byte >> 4);
-    const long long b = p.block_base + (e >> p.bs_log2);
-    float am;
-    if constexpr (DQ) am = __fadd_rn(__fmul_rn(p.sc.code2[p.sc.qabsmax[b]], p.sc.absmax2[b >> p.bs2_log2]), offset);
-    else am = p.sc.absmax[b];
-    float c;
-    if (p.lut) c = s_lut[nib];
-    else if (quant_type == QZ_NF4) c = kNF4[nib];
-    else c = (nib & 8u ? -1.0f : 1.0f) * dequant_fp4_tree(nib & 7u, 1.0f);
-    acc = fmaf(load_f32<DT>(p.x, k), __fmul_rn(c, am), acc);
-  }
-  acc = wave_sum_last(acc);
-  if (lane == kWave - 1) {
-    if (p.bias) acc += load_f32<DT>(p.bias, row);
-    store_f32<DT>(p.y, row, add_res<DT>(acc, p.res, row));
-  }
+  gemv_generic_body<DQ, DT>(p, quant_type);
 }
 
 // ---------------------------------------------------------------------------

@@ -175,6 +175,15 @@ struct GemvParams {
   const void *res;   // residual [M] added after the output rounding (y = round(round(x W^T) + res)), or nullptr
 };
 
+// LoRA adapter operand of a decode GEMV (LORA kernels, lora.hip): y[row] += sum_j B[row][j] * t[j],
+// B [M, r] row-major in the activation dtype, t fp32 [r] = scaling * (A x') from qz_lora_shrink.
+// r = 0 (a grouped segment without an adapter): nothing is added; B and t must still be readable.
+struct LoraOp {
+  const void *B;
+  const float *t;
+  int r;
+};
+
 __device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float c) {
   return __builtin_amdgcn_fdot2(__builtin_bit_cast(h2_t, a), __builtin_bit_cast(h2_t, b), c, false);
 }
@@ -572,6 +581,9 @@ struct GemvGroup {
   int nseg;
   int total;
 };
+struct LoraGroup {
+  LoraOp seg[kMaxSeg];
+};
 
 // The decode GEMV body.
 //  DQ: double-quantised scales; DT: activation dtype; R rows per wave; WK waves along K; NW waves
@@ -585,10 +597,15 @@ struct GemvGroup {
 //  step 2's issue (profiles/r4_gemv_two_step.txt); PS (pair launches with the norm): persistent
 //  workgroups -- each takes row blocks blockIdx.x, + gridDim.x, ..., so its prologue (byte table,
 //  code2, the normalised x) is paid once, and the next block's first step is issued before the
-//  current block's epilogue.
+//  current block's epilogue; LORA (the *_lora kernels of lora.hip only; every other kernel compiles
+//  none of it): in the wave that owns a row's first K-step, lane j < r adds B[row][j] * t[j] /
+//  out_scale to the row's accumulator before the wave reduction, which then carries the adapter
+//  term for free; its R + 1 small loads go out with the first weight loads.
 template <bool DQ, int DT, int R, int WK, int NW, bool FS, bool CL, bool WT, bool NRM, bool PAIR, bool TWO, bool PS,
-          int STAMP = 0>
-__device__ __forceinline__ void gemv_body(const GemvParams &p_in, const int block, const GemvParams *pair = nullptr) {
+          int STAMP = 0, bool LORA = false>
+__device__ __forceinline__ void gemv_body(const GemvParams &p_in, const int block, const GemvParams *pair = nullptr,
+                                          const LoraOp *lora = nullptr) {
+  static_assert(!LORA || (!PAIR && DT != QZ_DT_F32), "adapter operand: single / grouped launches, 16-bit activations");
   static_assert(!NRM || (NW == 4 && FS && DT != QZ_DT_F32), "fused pre-norm: 4 waves, full steps, 16-bit activations");
   static_assert(!PAIR || (NW == 4 && WK == 1 && DT != QZ_DT_F32), "pair: 4 waves, WK = 1, 16-bit activations");
   static_assert(!PS || (PAIR && FS), "persistent form: pair launches, full steps");
@@ -665,6 +682,24 @@ __device__ __forceinline__ void gemv_body(const GemvParams &p_in, const int bloc
   Loads cur, other;
   int s = wk;
   cur.issue(p, row0, s < nsteps ? s : 0, lane, row_bytes);
+  // 2b. LORA: lane j's B[row][j] of the R rows and t[j], behind the first weight loads.  Branch-free
+  // like the step loads: lanes past the rank (and the waves of later K-splits) read element 0 and
+  // are zeroed when the term is added
+  float lo_b[LORA ? R : 1], lo_t = 0.0f;
+  bool lo_on = false;
+  if constexpr (LORA) {
+    const int lr = keep_s(lora->r);
+    const char *lB = reinterpret_cast<const char *>(keep_sp(lora->B));
+    const float *lt = keep_sp(lora->t);
+    lo_on = lane < lr && wk == 0;
+    const int j = lo_on ? lane : 0;
+    lo_t = lt[j];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const size_t row = (size_t)min(row0 + r, p.M - 1);  // wave-uniform
+      lo_b[r] = load_f32<DT>(lB + row * (size_t)lr * 2u, j);
+    }
+  }
   const bool have = s < nsteps;
   const int n_my = have ? (nsteps - wk + WK - 1) / WK : 0;  // this wave's steps: s = wk, wk + WK, ...
   // 3. stage the code table (waits only for the code load: it was issued first)
@@ -874,6 +909,11 @@ __device__ __forceinline__ void gemv_body(const GemvParams &p_in, const int bloc
     }
   }
 
+  if constexpr (LORA) {  // pre-divided by out_scale (a power of two but for FP4's 1/12): the epilogue scales it back
+    const float inv = __fdiv_rn(1.0f, out_scale);
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = lo_on ? fmaf(__fmul_rn(lo_b[r], lo_t), inv, acc[r]) : acc[r];
+  }
   QZ_STAMP(3);
   if constexpr (PAIR) {  // gate (waves 0-1) and up (waves 2-3) of the same rows meet in LDS
     float v[R];
@@ -955,6 +995,44 @@ __device__ __forceinline__ void gemv_body(const GemvParams &p_in, const int bloc
       if (p.bias) v += load_f32<DT>(p.bias, row);
       store_f32<DT>(p.y, row, add_res<DT>(v, p.res, row));
     }
+  }
+}
+
+// Generic path for shapes the vector kernel does not cover (K % 32 != 0,
+// odd K, blocksize < 32): one wave per row, flat element addressing exactly
+// as the reference (e = r*K + k, byte e>>1, high nibble for even e).  LORA: lane j < r adds
+// B[row][j] * t[j] before the wave reduction.
+template <bool DQ, int DT, bool LORA = false>
+__device__ __forceinline__ void gemv_generic_body(const GemvParams &p, int quant_type, const LoraOp *lora = nullptr) {
+  __shared__ float s_lut[16];
+  if (threadIdx.x < 16) s_lut[threadIdx.x] = p.lut ? p.lut[threadIdx.x] : 0.0f;
+  __syncthreads();
+  const int lane = threadIdx.x & (kWave - 1);
+  const int row = blockIdx.x * 4 + threadIdx.x / kWave;
+  if (row >= p.M) return;
+  const float offset = DQ ? *p.sc.offset : 0.0f;
+  float acc = 0.0f;
+  for (int k = lane; k < p.K; k += kWave) {
+    const long long e = (long long)row * p.K + k;
+    const uint32_t byte = p.B[e >> 1];
+    const uint32_t nib = (e & 1) ? (byte & 0xFu) : (byte >> 4);
+    const long long b = p.block_base + (e >> p.bs_log2);
+    float am;
+    if constexpr (DQ) am = __fadd_rn(__fmul_rn(p.sc.code2[p.sc.qabsmax[b]], p.sc.absmax2[b >> p.bs2_log2]), offset);
+    else am = p.sc.absmax[b];
+    float c;
+    if (p.lut) c = s_lut[nib];
+    else if (quant_type == QZ_NF4) c = kNF4[nib];
+    else c = (nib & 8u ? -1.0f : 1.0f) * dequant_fp4_tree(nib & 7u, 1.0f);
+    acc = fmaf(load_f32<DT>(p.x, k), __fmul_rn(c, am), acc);
+  }
+  if constexpr (LORA) {
+    if (lane < lora->r) acc = fmaf(load_f32<DT>(lora->B, (long long)row * lora->r + lane), lora->t[lane], acc);
+  }
+  acc = wave_sum_last(acc);
+  if (lane == kWave - 1) {
+    if (p.bias) acc += load_f32<DT>(p.bias, row);
+    store_f32<DT>(p.y, row, add_res<DT>(acc, p.res, row));
   }
 }
 

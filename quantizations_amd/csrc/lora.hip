@@ -1,0 +1,391 @@
+// lora.hip -- LoRA adapters on the 4-bit decode GEMVs (batch-1 decode, 16-bit activations).
+//
+// A layer with weight W [M, K] (4-bit) and an adapter A [r, K], B [M, r], scaling computes
+//   t[j] = scaling * sum_k A[j,k] * x'[k]                         (fp32, never rounded to 16 bit)
+//   y[m] = round((W x')[m] (+ bias[m]) + sum_j B[m,j] * t[j])     (+ the residual epilogue as before)
+// in two launches instead of the base launch plus four or more torch ops:
+//
+//  * qz_lora_shrink: t for every adapter that reads the same x (the q/k/v or gate/up of a layer),
+//    optionally with the RMSNorm prologue of the fused-norm GEMV (k_rmsnorm's arithmetic, so t is
+//    formed from the bits that GEMV multiplies).  One 256-thread workgroup per rank row, K split over
+//    its threads in 16-B chunks: the operand is r x K x 2 bytes (128 KiB at r = 16, K = 4096), far
+//    below what fills the chip, so the launch is latency-bound and the geometry keeps it to one
+//    dependent memory round trip per pass, one reduction and no second launch or atomics.
+//  * the *_lora GEMV kernels: gemv_body<..., LORA> (gemv_core.h) -- lane j < r of the wave that owns a
+//    row adds B[row][j] * t[j] / out_scale into the row's accumulator before the wave reduction.
+//    They are kernels of their own, so the kernels of layers without an adapter are compiled from
+//    exactly the code they had, and scaling (read from device memory by the shrink launch only) is
+//    not baked into a captured graph.
+#include "gemv_core.h"
+
+namespace qz {
+
+template <bool DQ, int DT, int R, int WK, int NW, bool FS, bool CL, bool WT, bool TWO>
+__global__ __launch_bounds__(NW * 64) void k_gemv_4bit_lora(GemvParams p, LoraOp l) {
+  gemv_body<DQ, DT, R, WK, NW, FS, CL, WT, false, false, TWO, false, 0, true>(p, blockIdx.x, nullptr, &l);
+}
+
+template <bool DQ, int DT, int R, int WK, bool FS, bool CL, bool NRM, bool TWO>
+__global__ __launch_bounds__(256) void k_gemv_4bit_grouped_lora(GemvGroup g, LoraGroup lg) {
+  const int b = blockIdx.x;
+  int s = 0;
+#pragma unroll
+  for (int i = 1; i < kMaxSeg; ++i)
+    if (i < g.nseg && b >= g.start[i]) s = i;
+  s = __builtin_amdgcn_readfirstlane(s);
+  // copied out before load_params launders them (see k_gemv_4bit_grouped)
+  const GemvParams seg = g.seg[s];
+  const LoraOp lo = lg.seg[s];
+  const int start = g.start[s];
+  gemv_body<DQ, DT, R, WK, 4, FS, CL, false, NRM, false, TWO, false, 0, true>(seg, b - start, nullptr, &lo);
+}
+
+template <bool DQ, int DT>
+__global__ __launch_bounds__(256) void k_gemv_4bit_generic_lora(GemvParams p, int quant_type, LoraOp l) {
+  gemv_generic_body<DQ, DT, true>(p, quant_type, &l);
+}
+
+// ---------------------------------------------------------------------------
+// shrink: t = scaling * A x'
+// ---------------------------------------------------------------------------
+
+struct ShrinkArgs {
+  const void *A[kMaxSeg];
+  const float *scaling[kMaxSeg];
+  int start[kMaxSeg];   // first workgroup (= first rank row over all adapters) of adapter i
+  int t_off[kMaxSeg];
+  int nseg;
+  int K;
+  const void *x;
+  const void *nw;       // NRM: the RMSNorm weight [K]
+  float eps;
+  float *t;
+};
+
+// fp32 dot of the 8 16-bit elements of two 16-B chunks, in element order
+template <int DT> __device__ __forceinline__ float chunk_dot16(const u32x4 &a, const u32x4 &x, float acc) {
+  const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, xw[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const uint32_t ab = (aw[j >> 1] >> (16 * (j & 1))) & 0xFFFFu, xb = (xw[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
+    const float af = DT == QZ_DT_F16 ? __half2float(__ushort_as_half((unsigned short)ab)) : __uint_as_float(ab << 16);
+    const float xf = DT == QZ_DT_F16 ? __half2float(__ushort_as_half((unsigned short)xb)) : __uint_as_float(xb << 16);
+    acc = fmaf(af, xf, acc);
+  }
+  return acc;
+}
+
+// One workgroup per rank row j of adapter s: thread t takes the 16-B chunks t, t + 256, ... of the
+// row.  The first kHeld chunks of x, A (and the norm weight) are loaded up front and stay in
+// registers (K <= 4096: all of them), so the norm's reduction waits for one memory round trip and
+// the dot for none.  NRM: the sum of squares, rs and x' exactly as k_rmsnorm / the fused-norm GEMV
+// prologue form them (norm_chunk_ss / norm_chunk_apply, the same per-thread chunk order for 256
+// threads, the same butterfly and partial order).
+template <int DT, bool NRM>
+__global__ __launch_bounds__(256) void k_lora_shrink(ShrinkArgs a) {
+  constexpr int kHeld = 2;
+  __shared__ float s_nss[4];
+  __shared__ float s_dot[4];
+  const int b = blockIdx.x;
+  int s = 0;
+#pragma unroll
+  for (int i = 1; i < kMaxSeg; ++i)
+    if (i < a.nseg && b >= a.start[i]) s = i;
+  s = __builtin_amdgcn_readfirstlane(s);
+  const int j = b - a.start[s];
+  const int K = a.K, nchunk = K >> 3;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const u32x4 *xp = reinterpret_cast<const u32x4 *>(a.x);
+  const u32x4 *wp = reinterpret_cast<const u32x4 *>(a.nw);
+  const u32x4 *ap = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(a.A[s]) + (size_t)j * (size_t)K * 2u);
+  const float scaling = *a.scaling[s];
+
+  u32x4 xh[kHeld], ah[kHeld], wh[NRM ? kHeld : 1];
+#pragma unroll
+  for (int i = 0; i < kHeld; ++i) {
+    const int c = tid + 256 * i;
+    if (c < nchunk) {
+      xh[i] = xp[c];
+      ah[i] = ap[c];
+      if constexpr (NRM) wh[i] = wp[c];
+    }
+  }
+  float rs = 0.0f;
+  if constexpr (NRM) {
+    float ss = 0.0f;
+#pragma unroll
+    for (int i = 0; i < kHeld; ++i)
+      if (tid + 256 * i < nchunk) ss = norm_chunk_ss<DT>(xh[i], ss);
+    for (int c = tid + 256 * kHeld; c < nchunk; c += 256) ss = norm_chunk_ss<DT>(xp[c], ss);
+    ss = norm_wave_sum(ss);
+    if (lane == 0) s_nss[wave] = ss;
+    __syncthreads();
+    const float tot = __fadd_rn(__fadd_rn(s_nss[0], s_nss[1]), __fadd_rn(s_nss[2], s_nss[3]));
+    rs = rsqrtf(__fadd_rn(__fmul_rn(tot, 1.0f / (float)K), a.eps));
+  }
+  float acc = 0.0f;
+#pragma unroll
+  for (int i = 0; i < kHeld; ++i) {
+    if (tid + 256 * i < nchunk) {
+      u32x4 xv = xh[i];
+      if constexpr (NRM) xv = norm_chunk_apply<DT>(xv, wh[i], rs);
+      acc = chunk_dot16<DT>(ah[i], xv, acc);
+    }
+  }
+  for (int c = tid + 256 * kHeld; c < nchunk; c += 256) {
+    u32x4 xv = xp[c];
+    if constexpr (NRM) xv = norm_chunk_apply<DT>(xv, wp[c], rs);
+    acc = chunk_dot16<DT>(ap[c], xv, acc);
+  }
+  acc = norm_wave_sum(acc);
+  if (lane == 0) s_dot[wave] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    const float d = __fadd_rn(__fadd_rn(s_dot[0], s_dot[1]), __fadd_rn(s_dot[2], s_dot[3]));
+    a.t[a.t_off[s] + j] = __fmul_rn(scaling, d);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+
+// the geometry switch of gemv.hip's launch_vec, on the adapter-carrying kernels
+template <bool DQ, int DT, bool FS, bool CL>
+static void launch_vec_lora(const GemvParams &p, const LoraOp &l, int R, int WK, hipStream_t s) {
+  const int RG = 4 / WK;
+  const unsigned grid = (unsigned)((p.M + R * RG - 1) / (R * RG));
+#define QZ_GV(RR, WW, TWO_)                                                                                      \
+  hipLaunchKernelGGL((k_gemv_4bit_lora<DQ, DT, RR, WW, 4, FS, CL, false, (WW == 1 && TWO_)>), dim3(grid), dim3(256), \
+                     0, s, p, l)
+#define QZ_GV_RW(TWO_)                        \
+  do {                                        \
+    if (R == 4 && WK == 2) QZ_GV(4, 2, TWO_); \
+    else if (R == 4) QZ_GV(4, 1, TWO_);       \
+    else if (R == 2) QZ_GV(2, 1, TWO_);       \
+    else if (WK == 1) QZ_GV(1, 1, TWO_);      \
+    else if (WK == 2) QZ_GV(1, 2, TWO_);      \
+    else QZ_GV(1, 4, TWO_);                   \
+  } while (0)
+  if constexpr (FS) {
+    if (two_steps(p.K, WK, true)) { QZ_GV_RW(true); return; }
+  }
+  // the 8-wave exact-code form of long rows (gemv.hip launch_vec)
+  if constexpr (FS && CL && DT == QZ_DT_F16) {
+    if (WK == 1 && (R == 2 || R == 4) && p.K >= 14336 && gemv_knobs().wide8) {
+      const unsigned g8 = (unsigned)((p.M + R * 8 - 1) / (R * 8));
+      if (R == 4) hipLaunchKernelGGL((k_gemv_4bit_lora<DQ, DT, 4, 1, 8, FS, CL, true, false>), dim3(g8), dim3(512), 0, s, p, l);
+      else hipLaunchKernelGGL((k_gemv_4bit_lora<DQ, DT, 2, 1, 8, FS, CL, true, false>), dim3(g8), dim3(512), 0, s, p, l);
+      return;
+    }
+  }
+  QZ_GV_RW(false);
+#undef QZ_GV_RW
+#undef QZ_GV
+}
+
+template <bool DQ, bool FS>
+static void dispatch_lora(const GemvParams &p, const LoraOp &l, int dtype, bool cl, int R, int WK, hipStream_t s) {
+  if (dtype == QZ_DT_BF16) launch_vec_lora<DQ, QZ_DT_BF16, FS, false>(p, l, R, WK, s);
+  else if (cl) launch_vec_lora<DQ, QZ_DT_F16, FS, true>(p, l, R, WK, s);
+  else launch_vec_lora<DQ, QZ_DT_F16, FS, false>(p, l, R, WK, s);
+}
+
+static bool lora_args_ok(const void *lora_B, int r, const float *t) {
+  return lora_B && t && r >= 1 && r <= QZ_LORA_MAX_RANK;
+}
+
+}  // namespace qz
+
+using namespace qz;
+
+extern "C" int qz_gemv_4bit_lora(int M, int K, const void *x, int dtype, const unsigned char *B, int quant_type,
+                                 int blocksize, const float *absmax, const unsigned char *qabsmax,
+                                 const float *absmax2, const float *code2, const float *offset, int blocksize2,
+                                 long long block_base, const float *lut, const void *bias, const void *residual,
+                                 const void *lora_B, int r, const float *t, void *y, void *stream) {
+  if (!lora_args_ok(lora_B, r, t)) return QZ_ERR_ARG;
+  if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) return QZ_ERR_DTYPE;
+  GemvParams p;
+  bool vec_ok;
+  const int st = make_params(M, K, x, dtype, B, quant_type, blocksize, absmax, qabsmax, absmax2, code2, offset,
+                             blocksize2, block_base, lut, bias, y, &p, &vec_ok);
+  if (st != QZ_OK) return st;
+  p.res = residual;
+  if (M == 0) return QZ_OK;
+  const LoraOp l{lora_B, t, r};
+  const bool dq = qabsmax != nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  const bool cl = exact_codes(quant_type, lut) && dtype == QZ_DT_F16;
+  quant_type &= ~QZ_EXACT_CODES;
+  if (!vec_ok) {
+    const unsigned grid = (unsigned)((M + 3) / 4);
+    if (K == 0) return QZ_ERR_SHAPE;
+#define QZ_GG(DQ_, DT_) \
+  hipLaunchKernelGGL((k_gemv_4bit_generic_lora<DQ_, DT_>), dim3(grid), dim3(256), 0, s, p, quant_type, l)
+    if (dq) { if (dtype == QZ_DT_F16) QZ_GG(true, QZ_DT_F16); else QZ_GG(true, QZ_DT_BF16); }
+    else { if (dtype == QZ_DT_F16) QZ_GG(false, QZ_DT_F16); else QZ_GG(false, QZ_DT_BF16); }
+#undef QZ_GG
+    QZ_LAUNCH_CHECK();
+    return QZ_OK;
+  }
+  int R, WK;
+  choose_geometry(M, K, dtype, &R, &WK);
+  set_tables(quant_type, lut, cl, dtype, &p);
+  const bool fs = full_steps(K, blocksize, blocksize2, dq, block_base);
+  if (fs) { if (dq) dispatch_lora<true, true>(p, l, dtype, cl, R, WK, s); else dispatch_lora<false, true>(p, l, dtype, cl, R, WK, s); }
+  else { if (dq) dispatch_lora<true, false>(p, l, dtype, cl, R, WK, s); else dispatch_lora<false, false>(p, l, dtype, cl, R, WK, s); }
+  QZ_LAUNCH_CHECK();
+  return QZ_OK;
+}
+
+// qz_gemv_4bit_grouped(_rmsnorm) with an adapter operand per segment (gemv.hip gemv_grouped_impl:
+// the same checks, geometry and declines)
+extern "C" int qz_gemv_4bit_grouped_lora(int nseg, const qz_gemv_segment *segs, const qz_lora_segment *lora,
+                                         const float *t, int K, const void *x, int dtype, int quant_type,
+                                         int blocksize, int blocksize2, const float *lut, const void *nw, float eps,
+                                         void *stream) {
+  if (nseg < 1 || nseg > QZ_GEMV_MAX_SEGMENTS || !segs || !lora || !t) return QZ_ERR_ARG;
+  if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) return QZ_ERR_DTYPE;
+  GemvGroup g;
+  LoraGroup lg;
+  g.nseg = nseg;
+  const bool cl = exact_codes(quant_type, lut) && dtype == QZ_DT_F16;
+  bool all_vec = true;
+  long long total_m = 0;
+  const bool dq = segs[0].qabsmax != nullptr;
+  for (int i = 0; i < nseg; ++i) {
+    const qz_gemv_segment &q = segs[i];
+    bool v;
+    const int st = make_params(q.M, K, x, dtype, q.B, quant_type, blocksize, q.absmax, q.qabsmax, q.absmax2, q.code2,
+                               q.offset, blocksize2, q.block_base, lut, q.bias, q.y, &g.seg[i], &v);
+    if (st != QZ_OK) return st;
+    if ((q.qabsmax != nullptr) != dq) return QZ_ERR_ARG;
+    if (lora[i].B) {
+      if (lora[i].r < 1 || lora[i].r > QZ_LORA_MAX_RANK || lora[i].t_offset < 0) return QZ_ERR_ARG;
+      lg.seg[i] = LoraOp{lora[i].B, t + lora[i].t_offset, lora[i].r};
+    } else {
+      lg.seg[i] = LoraOp{t, t, 0};   // no adapter: rank 0, the (unused) loads read t[0]
+    }
+    all_vec = all_vec && v;
+    total_m += q.M;
+  }
+  for (int i = nseg; i < kMaxSeg; ++i) lg.seg[i] = LoraOp{t, t, 0};
+  if (total_m == 0) return QZ_OK;
+  if (nw) {
+    if (!x || !all_vec || total_m > INT32_MAX || K % 8 != 0 || K > 16384 || ((uintptr_t)x | (uintptr_t)nw) % 16 != 0)
+      return QZ_ERR_SHAPE;
+    for (int i = 0; i < nseg; ++i) {
+      if (!full_steps(K, blocksize, blocksize2, dq, segs[i].block_base)) return QZ_ERR_SHAPE;
+      g.seg[i].nw = nw;
+      g.seg[i].eps = eps;
+    }
+  }
+  if (!all_vec || total_m > INT32_MAX) {  // odd shapes: one launch per segment (same results)
+    for (int i = 0; i < nseg; ++i) {
+      const qz_gemv_segment &q = segs[i];
+      const int rc = lora[i].B
+          ? qz_gemv_4bit_lora(q.M, K, x, dtype, q.B, quant_type, blocksize, q.absmax, q.qabsmax, q.absmax2, q.code2,
+                              q.offset, blocksize2, q.block_base, lut, q.bias, nullptr, lora[i].B, lora[i].r,
+                              t + lora[i].t_offset, q.y, stream)
+          : qz_gemv_4bit(q.M, K, x, dtype, q.B, quant_type, blocksize, q.absmax, q.qabsmax, q.absmax2, q.code2,
+                         q.offset, blocksize2, q.block_base, lut, q.bias, q.y, stream);
+      if (rc != QZ_OK) return rc;
+    }
+    return QZ_OK;
+  }
+  int R, WK;
+  choose_geometry((int)total_m, K, dtype, &R, &WK);
+  if (nw && gemv_knobs().norm_r && WK == 1) R = gemv_knobs().norm_r;
+  const int rows_per_block = R * (4 / WK);
+  int blocks = 0;
+  for (int i = 0; i < nseg; ++i) {
+    set_tables(quant_type & ~QZ_EXACT_CODES, lut, cl, dtype, &g.seg[i]);
+    g.start[i] = blocks;
+    blocks += (g.seg[i].M + rows_per_block - 1) / rows_per_block;
+  }
+  for (int i = nseg; i < kMaxSeg; ++i) g.start[i] = blocks;
+  g.total = blocks;
+  if (nw && blocks > kNormMaxBlocks) return QZ_ERR_SHAPE;
+  if (nw && WK != 1 && (long long)blocks * K > kNormSplitMaxValues) return QZ_ERR_SHAPE;
+  bool all_fs = true;
+  for (int i = 0; i < nseg; ++i) all_fs = all_fs && full_steps(K, blocksize, blocksize2, dq, segs[i].block_base);
+  hipStream_t s = (hipStream_t)stream;
+  const bool two = two_steps(K, WK, all_fs || nw);
+  const size_t lds = nw ? (size_t)K * 2 : 0;
+#define QZ_GR1(DQ_, DT_, RR, WW, FS_, CL_, NRM_)                                                                   \
+  do {                                                                                                           \
+    if (FS_ && two && WW == 1)                                                                                   \
+      hipLaunchKernelGGL((k_gemv_4bit_grouped_lora<DQ_, DT_, RR, WW, FS_, CL_, NRM_, (FS_ && WW == 1)>), dim3(blocks), \
+                         dim3(256), lds, s, g, lg);                                                              \
+    else hipLaunchKernelGGL((k_gemv_4bit_grouped_lora<DQ_, DT_, RR, WW, FS_, CL_, NRM_, false>), dim3(blocks),        \
+                            dim3(256), lds, s, g, lg);                                                           \
+  } while (0)
+#define QZ_GR_RW(DQ_, DT_, FS_, CL_, NRM_)                         \
+  do {                                                           \
+    if (R == 4 && WK == 2) QZ_GR1(DQ_, DT_, 4, 2, FS_, CL_, NRM_); \
+    else if (R == 4) QZ_GR1(DQ_, DT_, 4, 1, FS_, CL_, NRM_);       \
+    else if (R == 2) QZ_GR1(DQ_, DT_, 2, 1, FS_, CL_, NRM_);       \
+    else if (WK == 1) QZ_GR1(DQ_, DT_, 1, 1, FS_, CL_, NRM_);      \
+    else if (WK == 2) QZ_GR1(DQ_, DT_, 1, 2, FS_, CL_, NRM_);      \
+    else QZ_GR1(DQ_, DT_, 1, 4, FS_, CL_, NRM_);                   \
+  } while (0)
+#define QZ_GR_DT(DQ_, FS_, NRM_)                                                                                      \
+  do {                                                                                                              \
+    if (dtype == QZ_DT_F16) { if (cl) QZ_GR_RW(DQ_, QZ_DT_F16, FS_, true, NRM_); else QZ_GR_RW(DQ_, QZ_DT_F16, FS_, false, NRM_); } \
+    else QZ_GR_RW(DQ_, QZ_DT_BF16, FS_, false, NRM_);                                                              \
+  } while (0)
+  if (nw) { if (dq) QZ_GR_DT(true, true, true); else QZ_GR_DT(false, true, true); }
+  else if (all_fs) { if (dq) QZ_GR_DT(true, true, false); else QZ_GR_DT(false, true, false); }
+  else { if (dq) QZ_GR_DT(true, false, false); else QZ_GR_DT(false, false, false); }
+#undef QZ_GR_DT
+#undef QZ_GR_RW
+#undef QZ_GR1
+  QZ_LAUNCH_CHECK();
+  return QZ_OK;
+}
+
+extern "C" int qz_lora_shrink(int nseg, const qz_lora_shrink_segment *segs, int K, const void *x, int dtype,
+                              const void *norm_weight, float eps, float *t, void *stream) {
+  if (nseg < 1 || nseg > QZ_GEMV_MAX_SEGMENTS || !segs || !x || !t || K < 0) return QZ_ERR_ARG;
+  if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) return QZ_ERR_DTYPE;
+  ShrinkArgs a;
+  int blocks = 0;
+  uintptr_t align = (uintptr_t)x | (uintptr_t)norm_weight;
+  for (int i = 0; i < kMaxSeg; ++i) {
+    if (i < nseg) {
+      const qz_lora_shrink_segment &q = segs[i];
+      if (!q.A || !q.scaling || q.r < 1 || q.r > QZ_LORA_MAX_RANK || q.t_offset < 0) return QZ_ERR_ARG;
+      a.A[i] = q.A;
+      a.scaling[i] = q.scaling;
+      a.start[i] = blocks;
+      a.t_off[i] = q.t_offset;
+      blocks += q.r;
+      align |= (uintptr_t)q.A;
+    } else {
+      a.A[i] = nullptr;
+      a.scaling[i] = nullptr;
+      a.start[i] = blocks;
+      a.t_off[i] = 0;
+    }
+  }
+  // 16-B chunks of 8 elements: rows of A start on a chunk when K % 8 == 0
+  if (K == 0 || K % 8 != 0 || align % 16 != 0) return QZ_ERR_SHAPE;
+  a.nseg = nseg;
+  a.K = K;
+  a.x = x;
+  a.nw = norm_weight;
+  a.eps = eps;
+  a.t = t;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)blocks), block(256);
+  if (dtype == QZ_DT_F16) {
+    if (norm_weight) hipLaunchKernelGGL((k_lora_shrink<QZ_DT_F16, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_lora_shrink<QZ_DT_F16, false>), grid, block, 0, s, a);
+  } else {
+    if (norm_weight) hipLaunchKernelGGL((k_lora_shrink<QZ_DT_BF16, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_lora_shrink<QZ_DT_BF16, false>), grid, block, 0, s, a);
+  }
+  QZ_LAUNCH_CHECK();
+  return QZ_OK;
+}

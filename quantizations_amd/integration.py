@@ -579,6 +579,71 @@ def unfuse_decode_glue(model: nn.Module) -> None:
 # pre-quantised checkpoints
 # ---------------------------------------------------------------------------
 
+_LORA_PREFIX = "base_model.model."
+
+
+def load_lora_adapter(model: nn.Module, path: str) -> int:
+    """Give the Linear4bit layers of `model` the LoRA adapter of a peft adapter directory
+    (``adapter_config.json`` + ``adapter_model.safetensors``; peft itself is not needed).  Keys
+    ``base_model.model.<module path>.lora_A.weight`` / ``....lora_B.weight`` map to
+    ``Linear4bit.set_adapter`` of that module; scaling = lora_alpha / r, or lora_alpha / sqrt(r)
+    with ``use_rslora``, r taken from each layer's tensors (so ``rank_pattern`` works).  DoRA,
+    ``alpha_pattern``, trained biases and ``modules_to_save`` are refused (NotImplementedError
+    naming the field); a key whose module is not a Linear4bit of the model raises KeyError.
+    Returns the number of layers given an adapter."""
+    import json
+    import math
+    import os
+
+    from safetensors.torch import load_file
+
+    with open(os.path.join(path, "adapter_config.json")) as f:
+        cfg = json.load(f)
+    if cfg.get("use_dora"):
+        raise NotImplementedError("load_lora_adapter: use_dora adapters are not supported")
+    if cfg.get("alpha_pattern"):
+        raise NotImplementedError("load_lora_adapter: alpha_pattern is not supported")
+    if cfg.get("bias", "none") != "none":
+        raise NotImplementedError(f"load_lora_adapter: bias = {cfg['bias']!r} is not supported (only \"none\")")
+    if cfg.get("modules_to_save"):
+        raise NotImplementedError("load_lora_adapter: modules_to_save is not supported")
+    alpha = float(cfg.get("lora_alpha", cfg.get("r", 1)))
+    rslora = bool(cfg.get("use_rslora", False))
+    tensors = load_file(os.path.join(path, "adapter_model.safetensors"))
+    modules = dict(model.named_modules())
+    pairs = {}
+    for key, val in tensors.items():
+        for part, suffix in (("A", ".lora_A.weight"), ("B", ".lora_B.weight")):
+            if key.startswith(_LORA_PREFIX) and key.endswith(suffix):
+                pairs.setdefault(key[len(_LORA_PREFIX):-len(suffix)], {})[part] = val
+                break
+        else:
+            raise KeyError(f"load_lora_adapter: unexpected key {key!r}")
+    targets = cfg.get("target_modules")
+    for name, ab in pairs.items():
+        mod = modules.get(name)
+        if not isinstance(mod, Linear4bit):
+            raise KeyError(f"load_lora_adapter: {name!r} is not a Linear4bit of the model")
+        if "A" not in ab or "B" not in ab:
+            raise KeyError(f"load_lora_adapter: {name!r} lacks lora_A.weight or lora_B.weight")
+        if isinstance(targets, (list, tuple)) and targets and not any(name == t or name.endswith("." + t) for t in targets):
+            raise KeyError(f"load_lora_adapter: {name!r} is not among target_modules {list(targets)}")
+    for name, ab in pairs.items():   # every key checked: now set them
+        r = ab["A"].shape[0]
+        modules[name].set_adapter(ab["A"], ab["B"], alpha / math.sqrt(r) if rslora else alpha / r)
+    return len(pairs)
+
+
+def unload_lora_adapter(model: nn.Module) -> int:
+    """Remove every adapter set by load_lora_adapter / Linear4bit.set_adapter.  Returns how many."""
+    n = 0
+    for m in model.modules():
+        if isinstance(m, Linear4bit) and m.adapter is not None:
+            m.clear_adapter()
+            n += 1
+    return n
+
+
 def save_quantized(model: nn.Module, path: str) -> None:
     """Write `model`'s state dict (Linear4bit weights as packed bytes + their
     quant_state in the bnb key layout) to a safetensors file."""

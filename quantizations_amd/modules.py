@@ -13,7 +13,7 @@ import weakref
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, lora
 from .core import (MT_MAX_TOKENS, Params4bit, QuantState, dequantize_4bit, exact_codes_for, gemm_4bit,
                    gemm_4bit_grouped, gemv_4bit, gemv_4bit_grouped, gemv_4bit_pair_silu, grouped_tokens_ok)
 
@@ -88,14 +88,29 @@ def _linear4bit_group_compute(group: DecodeGroup, x: torch.Tensor):
     for m in group.members:
         bias = None if m.bias is None else m.bias.to(xin.dtype)
         items.append((m.weight, m.weight.quant_state, bias))
+    ads = [m.adapter for m in group.members]
+    has_ad = any(a is not None for a in ads)
+    if has_ad and fused_norm and not all(lora.fused_ok(a, xin) for a in ads if a is not None):
+        # an adapter the fused route does not take needs the normalised x for its torch ops
+        x = norm[2](x)
+        xin = m0._input(x)
+        fused_norm = False
     if xin.numel() == xin.shape[-1]:
+        lo = None
+        if has_ad and all(lora.fused_ok(a, xin) for a in ads if a is not None):
+            # one shrink launch for all of the group's adapters, then the grouped launch carries B . t
+            t, offs = lora.shrink(xin, ads, norm=norm[:2] if fused_norm else None)
+            lo = (t, [None if a is None else (a.B, o) for a, o in zip(ads, offs)])
+            has_ad = False
         outs = gemv_4bit_grouped(xin, items, exact_codes=exact_codes_for(m0.compute_dtype),
-                                 norm=norm[:2] if fused_norm else None)
+                                 norm=norm[:2] if fused_norm else None, lora=lo)
     elif grouped_tokens_ok(xin, items):
         outs = gemm_4bit_grouped(xin, items)
     else:  # shapes the multi-token kernel does not take: each member as it would run alone
         outs = [matmul_4bit(xin, w, bias=b, quant_state=st, exact_codes=exact_codes_for(m0.compute_dtype))
                 for w, st, b in items]
+    if has_ad:   # the composed path: torch ops on the members' (normalised) input
+        outs = [o if a is None else o + lora.composed_term(a, xin, o.dtype) for o, a in zip(outs, ads)]
     return [o if o.dtype == inp_dtype else o.to(inp_dtype) for o in outs]
 
 
@@ -109,7 +124,7 @@ def linear4bit_silu_pair(group: DecodeGroup, x: torch.Tensor):
     if not (x.is_cuda and x.numel() == x.shape[-1] and x.dtype in (torch.float16, torch.bfloat16)):
         return None
     for m in group.members:
-        if m.weight.quant_state is None:
+        if m.weight.quant_state is None or m.adapter is not None:   # adapters: grouped launch + silu_mul
             return None
         if not m.compute_type_is_set:
             m.set_compute_type(x)
@@ -138,6 +153,34 @@ class Linear4bit(nn.Linear):
         self.compute_type_is_set = False
         self.quant_state = None
         self.quant_storage = quant_storage
+
+    # -- LoRA adapter (lora.py): not a parameter or buffer, so not part of state_dict(); kept by
+    # copy.deepcopy (it lives in __dict__) --
+    @property
+    def adapter(self):
+        """The layer's lora.LoraAdapter, or None."""
+        return self.__dict__.get("_qz_adapter")
+
+    def set_adapter(self, A: torch.Tensor, B: torch.Tensor, scaling: float = 1.0) -> None:
+        """Serve base(x) + lora_B(lora_A(x)) * scaling: A = lora_A.weight [r, in], B = lora_B.weight
+        [out, r].  A second call with the same shapes and dtypes copies into the existing buffers,
+        so a captured graph serves the new adapter on its next replay."""
+        lora.check_shapes(A, B, self.out_features, self.in_features)
+        ad = self.adapter
+        if ad is not None and ad.matches(A, B):
+            ad.copy_(A, B, scaling)
+        else:
+            self.__dict__["_qz_adapter"] = lora.LoraAdapter(A, B, scaling, self.weight.device)
+
+    def clear_adapter(self) -> None:
+        self.__dict__.pop("_qz_adapter", None)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        ad = self.adapter
+        if ad is not None and self.weight.device.type != "meta":
+            ad.to(self.weight.device)   # the adapter follows the layer's device
+        return out
 
     def set_compute_type(self, x):
         """Reference modules.py:112-122: fp32/bf16 inputs select their own dtype."""
@@ -169,8 +212,16 @@ class Linear4bit(nn.Linear):
         inp_dtype = x.dtype
         xin = self._input(x)
         bias = None if self.bias is None else self.bias.to(xin.dtype)
+        ad = self.adapter
+        if ad is not None and lora.fused_ok(ad, xin):   # one token: shrink, then the GEMV carries B . t
+            t, _ = lora.shrink(xin, [ad])
+            out = gemv_4bit(xin, self.weight, state=qs, bias=bias, exact_codes=exact_codes_for(self.compute_dtype),
+                            lora=(ad.B, t))
+            return out if out.dtype == inp_dtype else out.to(inp_dtype)
         out = matmul_4bit(xin, self.weight, bias=bias, quant_state=qs,
                           exact_codes=exact_codes_for(self.compute_dtype))
+        if ad is not None:
+            out = out + lora.composed_term(ad, xin, out.dtype)
         return out if out.dtype == inp_dtype else out.to(inp_dtype)
 
     def forward_residual(self, x: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
@@ -184,10 +235,12 @@ class Linear4bit(nn.Linear):
             if not self.compute_type_is_set:
                 self.set_compute_type(x)
                 self.compute_type_is_set = True
-            if self._input(x) is x:
+            ad = self.adapter
+            if self._input(x) is x and (ad is None or lora.fused_ok(ad, x)):
                 bias = None if self.bias is None else self.bias.to(x.dtype)
+                lo = None if ad is None else (ad.B, lora.shrink(x, [ad])[0])
                 return gemv_4bit(x, self.weight, state=qs, bias=bias, exact_codes=exact_codes_for(self.compute_dtype),
-                                 residual=residual)
+                                 residual=residual, lora=lo)
         return residual + self(x)
 
     # -- checkpoints: bnb-compatible keys (QuantState.as_dict(packed=True)) --

@@ -379,6 +379,13 @@ class RowParallelLinear4bit(nn.Module):
 TP_BLOCKS = ((("q_proj", "k_proj", "v_proj"), "o_proj"), (("gate_proj", "up_proj"), "down_proj"))
 
 
+def _refuse_adapter(layer: nn.Module, what: str) -> None:
+    """Sharded LoRA adapters are not implemented: a layer that carries one is not sharded."""
+    if getattr(layer, "adapter", None) is not None:
+        raise NotImplementedError(f"{what}: the Linear4bit carries a LoRA adapter; sharded adapters are not "
+                                  "implemented (unload_lora_adapter first)")
+
+
 def apply_tensor_parallel(model: nn.Module, rank: Optional[int] = None, world_size: Optional[int] = None,
                           group=None, local_matmul: Optional[Callable] = None, gatherer=None) -> int:
     """Megatron-style TP pairing over the Linear4bit layers of a decoder
@@ -398,6 +405,8 @@ def apply_tensor_parallel(model: nn.Module, rank: Optional[int] = None, world_si
             mods = [parent._modules.get(nm) for nm in cols + (row,)]
             if any(not isinstance(m, Linear4bit) for m in mods):
                 continue
+            for m in mods:
+                _refuse_adapter(m, "apply_tensor_parallel")
             if hasattr(parent, "head_dim") and cols[0] == "q_proj":
                 hd = parent.head_dim
                 for m in mods[:3]:
@@ -421,6 +430,7 @@ def shard_model_linear4bit(model: nn.Module, rank: Optional[int] = None, world_s
 
     for name, child in list(model.named_children()):
         if isinstance(child, Linear4bit):
+            _refuse_adapter(child, "shard_model_linear4bit")
             model._modules[name] = RowShardedLinear4bit(child, rank, world_size, group, local_matmul,
                                                         gatherer=gatherer)
         else:

@@ -404,6 +404,44 @@ int qz_gemv_4bit_grouped_lora(int nseg, const qz_gemv_segment *segs, const qz_lo
                               int K, const void *x, int dtype, int quant_type, int blocksize, int blocksize2,
                               const float *lut, const void *norm_weight, float eps, void *stream);
 
+/* LoRA adapter banks on the multi-token launch (extension): 2..16 token rows X [T, K] (row stride
+ * ldx), each row on its own adapter of a bank, or on none.  A bank for one weight [M, K] is
+ * A [n, r, K] and B [n, M, r], contiguous, in the activation dtype, scaling fp32 [n] in device
+ * memory, 1 <= r <= QZ_LORA_MAX_RANK, 1 <= n <= QZ_LORA_MAX_ADAPTERS.  slot is a device int32
+ * array with at least ceil(T / tokens_per_slot) entries: row c uses adapter a = slot[c /
+ * tokens_per_slot] (tokens_per_slot >= 1); any a < 0 or a >= n means "no adapter for this row" and no
+ * address is formed from it; slot == NULL means adapter 0 for every row.  slot and scaling are
+ * only read, at run time, so a captured graph serves whatever they hold at replay.
+ *   t[c * t_stride + t_offset_i + j] = scaling_i[a] * sum_k A_i[a, j, k] * X[c, k]   fp32 (qz_lora_shrink_mt)
+ *   y[c, m] = round((W X_c)[m] (+ bias[m]) + sum_j B[a, m, j] * t[c, j])    (qz_gemm_4bit_grouped_lora) */
+#define QZ_LORA_MAX_ADAPTERS 256
+typedef struct qz_lora_bank_shrink_segment {
+  const void *A;        /* [n, r, K], the dtype of X, 16-B aligned */
+  const float *scaling; /* device, [n] */
+  int n;
+  int r;
+  int t_offset;         /* this bank's columns of t: [t_offset, t_offset + r) of every row */
+} qz_lora_bank_shrink_segment;
+/* t for 1..QZ_GEMV_MAX_SEGMENTS banks that read the same X, in one launch; t is [T, t_stride] fp32.
+ * Rows without an adapter get t = 0 written (t is never left uninitialised).  K % 8 == 0, ldx % 8
+ * == 0 and 16-B-aligned X and A, else QZ_ERR_SHAPE (nothing launched); 2 <= T <= 16. */
+int qz_lora_shrink_mt(int nseg, const qz_lora_bank_shrink_segment *segs, int T, int K, const void *X, int ldx,
+                      int dtype, const int *slot, int tokens_per_slot, float *t, int t_stride, void *stream);
+/* qz_gemm_4bit_grouped (nseg 1..4) with one bank operand per segment, parallel to segs: B == NULL =
+ * that segment has no bank.  A row whose slot selects no adapter, and every segment without a bank,
+ * get the plain launch's output bit for bit.  The adapter term is added to the fp32 row sums after
+ * the bias, in ascending j with fp32 FMAs, before the one output rounding.  Declines what
+ * qz_gemm_4bit_grouped declines, and a B that is not 16-B aligned (QZ_ERR_SHAPE). */
+typedef struct qz_lora_bank_segment {
+  const void *B; /* [n, M, r] of the activation dtype, or NULL */
+  int n;
+  int r;
+  int t_offset;
+} qz_lora_bank_segment;
+int qz_gemm_4bit_grouped_lora(int nseg, const qz_gemv_segment *segs, const qz_lora_bank_segment *lora, const float *t,
+                              int t_stride, const int *slot, int tokens_per_slot, int T, int K, const void *X, int ldx,
+                              int dtype, int quant_type, int blocksize, int blocksize2, void *stream);
+
 /* The launch-geometry measurement knobs in effect (QZ_GEMV_WIDE8, QZ_GROUPED_NORM_R, QZ_PAIR_R,
  * QZ_PAIR_WT, QZ_PAIR_PS, QZ_PAIR_WK1, and QZ_GEMM16_SCHED -- the schedule qz_gemm_16bit (default 971, persistent)
  * launches: environment variables read ONCE when the library is loaded) and the

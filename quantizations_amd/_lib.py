@@ -54,7 +54,19 @@ class LoraShrinkSegment(ctypes.Structure):
                 ("t_offset", ctypes.c_int)]
 
 
+class LoraBankShrinkSegment(ctypes.Structure):
+    """struct qz_lora_bank_shrink_segment (include/quantizations.h)."""
+    _fields_ = [("A", ctypes.c_void_p), ("scaling", ctypes.c_void_p), ("n", ctypes.c_int), ("r", ctypes.c_int),
+                ("t_offset", ctypes.c_int)]
+
+
+class LoraBankSegment(ctypes.Structure):
+    """struct qz_lora_bank_segment (include/quantizations.h)."""
+    _fields_ = [("B", ctypes.c_void_p), ("n", ctypes.c_int), ("r", ctypes.c_int), ("t_offset", ctypes.c_int)]
+
+
 LORA_MAX_RANK = 64  # QZ_LORA_MAX_RANK
+LORA_MAX_ADAPTERS = 256  # QZ_LORA_MAX_ADAPTERS
 
 # name -> argtypes (restype int unless noted); mirrors include/quantizations.h
 SIGNATURES = {
@@ -76,6 +88,8 @@ SIGNATURES = {
     "qz_lora_shrink": [_i, _p, _i, _p, _i, _p, _f, _p, _p],
     "qz_gemv_4bit_lora": [_i, _i, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _ll, _p, _p, _p, _p, _i, _p, _p, _p],
     "qz_gemv_4bit_grouped_lora": [_i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _p, _p, _f, _p],
+    "qz_lora_shrink_mt": [_i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _p],
+    "qz_gemm_4bit_grouped_lora": [_i, _p, _p, _p, _i, _p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p],
     "qz_decode_attention": [_i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p, _ll, _ll,
                             _p, _p, _p, _ll, _p, _f, _p],
     "qz_gemm_4bit": [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _ll, _p],

@@ -729,12 +729,18 @@ def grouped_tokens_ok(A: Tensor, items) -> bool:
                and (not it[1].nested or it[1].state2.blocksize == s0.state2.blocksize) for it in items)
 
 
-def gemm_4bit_grouped(A: Tensor, items) -> list:
+def gemm_4bit_grouped(A: Tensor, items, lora=None) -> list:
     """Batched decode over a few tokens (2..16) for several 4-bit weights that
     share A (q/k/v, gate/up of one layer), in ONE launch (qz_gemm_4bit_grouped).
     items: (B, state, bias[, block_base]) as for gemv_4bit_grouped; returns
     [y_i] of shape [..., M_i], each bit-identical to gemm_4bit(A, B_i, state_i,
-    bias_i) on the multi-token kernel.  grouped_tokens_ok() says when it applies."""
+    bias_i) on the multi-token kernel.  grouped_tokens_ok() says when it applies.
+
+    lora=(t, [None | (bank_B_i [n_i, M_i, r_i], t_offset_i)], slots, tokens_per_slot): the adapter
+    banks' expand in the launch's epilogue (qz_gemm_4bit_grouped_lora).  t fp32 [T, stride] is
+    lora.shrink_mt's output for the same A; row c of A uses adapter slots[c // tokens_per_slot]
+    (slots int32 on A's device, or None = adapter 0), any value outside [0, n_i) none.  Rows and
+    weights without an adapter get the plain launch's bits."""
     items = list(items)
     if not grouped_tokens_ok(A, items):
         raise ValueError("gemm_4bit_grouped needs 2..16 fp16/bf16 tokens, K % 256 == 0, 1..4 weights that share "
@@ -759,6 +765,34 @@ def gemm_4bit_grouped(A: Tensor, items) -> list:
         outs.append(y)
     s0 = items[0][1]
     bs2 = int(s0.state2.blocksize) if s0.nested else 0
+    if lora is not None:
+        t, entries, slots, tps = lora
+        tps = int(tps)
+        if len(entries) != len(items) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != T or \
+                not t.is_contiguous() or t.device != A.device or tps < 1:
+            raise ValueError(f"gemm_4bit_grouped: lora must be (t fp32 [{T}, stride], one entry per weight, slots, "
+                             "tokens_per_slot >= 1)")
+        if slots is not None and (slots.dtype != torch.int32 or slots.device != A.device or not slots.is_contiguous()
+                                  or slots.numel() < (T + tps - 1) // tps):
+            raise ValueError("gemm_4bit_grouped: slots must be a contiguous int32 tensor on the input's device with "
+                             "one entry per stream")
+        lsegs = (_lib.LoraBankSegment * len(items))()
+        for i, ent in enumerate(entries):
+            if ent is None:
+                lsegs[i] = _lib.LoraBankSegment(None, 0, 0, 0)
+                continue
+            lB, off = ent
+            if lB.dtype != A.dtype or lB.dim() != 3 or lB.shape[1] != items[i][1].shape[0] or \
+                    not lB.is_contiguous() or off < 0 or off + lB.shape[2] > t.shape[1]:
+                raise ValueError(f"gemm_4bit_grouped: lora entry {i} must be (B [n, M, r] contiguous {A.dtype}, "
+                                 "t_offset)")
+            lsegs[i] = _lib.LoraBankSegment(ptr(lB), int(lB.shape[0]), int(lB.shape[2]), int(off))
+        check(lib.qz_gemm_4bit_grouped_lora(len(items), ctypes.cast(segs, ctypes.c_void_p),
+                                            ctypes.cast(lsegs, ctypes.c_void_p), ptr(t), int(t.shape[1]), ptr(slots),
+                                            tps, T, K, ptr(A2), A2.stride(0), dtype_code(A.dtype),
+                                            _lib.QUANT_TYPES[s0.quant_type], s0.blocksize, bs2, _lib.stream_of(A)),
+              "gemm_4bit_grouped(lora)")
+        return [y.reshape(*lead, y.shape[-1]) for y in outs]
     check(lib.qz_gemm_4bit_grouped(len(items), ctypes.cast(segs, ctypes.c_void_p), T, K, ptr(A2), A2.stride(0),
                                    dtype_code(A.dtype), _lib.QUANT_TYPES[s0.quant_type], s0.blocksize, bs2,
                                    _lib.stream_of(A)), "gemm_4bit_grouped")

@@ -2158,8 +2158,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // zero row.  TB = 0: the direct fragment loads (kept for the microbenchmark).
 constexpr int kMtChunk = 256, kMtWaves = 8;
 constexpr int kMtXRow = kMtChunk * 2 + 16;  // padded LDS row of one token's chunk of X
-template <int QT, bool DQ, int DT, int TB = 0, int W = kMtWaves>
-__device__ __forceinline__ void mt_body(const GemmParams &p, const int block) {
+// LORA (the *_lora kernels only; every other instantiation leaves it false and passes no operand):
+// the expand of a LoRA adapter bank in the epilogue.  Token row c uses adapter a = slot[c / S]
+// (slot == nullptr: adapter 0); a outside [0, n) means no adapter for that row, and no address is
+// formed from it.  After the bias add the thread that owns (token c, row m) adds
+// sum_j B[a][m][j] * t[c][j] in ascending j with fp32 FMAs and rounds once; a row without an
+// adapter and a segment without a bank (B == nullptr) skip the adds, so they store the plain
+// launch's bits.
+struct MtLora {
+  const void *B;     // [n, M, r] of the activation dtype, 16-B aligned; nullptr: no bank
+  const float *t;    // this bank's t: row c at t[c * t_stride .. + r)  (qz_lora_shrink_mt)
+  const int *slot;   // [ceil(T / S)] adapter index per stream, or nullptr
+  int n, r, t_stride, S;
+};
+template <int QT, bool DQ, int DT, int TB = 0, int W = kMtWaves, bool LORA = false>
+__device__ __forceinline__ void mt_body(const GemmParams &p, const int block, const MtLora *lo = nullptr) {
   constexpr int XL = TB > 0 ? (TB + 1) / 2 : 1;  // staging loads per lane per chunk (two token rows each)
   __shared__ float s_code2[DQ ? 256 : 1];
   __shared__ f4_t s_red[W][64];
@@ -2281,6 +2294,32 @@ __device__ __forceinline__ void mt_body(const GemmParams &p, const int block) {
 #pragma unroll
       for (int w = 0; w < W; ++w) v += s_red[w][l][i];
       if (p.bias) v += load_f32<DT>(p.bias, m);
+      if constexpr (LORA) {
+        if (lo->B) {
+          const int a = lo->slot ? lo->slot[c / lo->S] : 0;
+          if (a >= 0 && a < lo->n) {
+            const int r = lo->r;
+            const float *tp = lo->t + (size_t)c * (size_t)lo->t_stride;
+            const size_t b0 = ((size_t)a * (size_t)p.M + (size_t)m) * (size_t)r;
+            int j = 0;
+            if ((r & 7) == 0) {  // rows of B are whole 16-B chunks: the same sum from 16-B loads
+              const v4u *bp = reinterpret_cast<const v4u *>(reinterpret_cast<const uint16_t *>(lo->B) + b0);
+              for (; j < r; j += 8) {
+                const v4u bv = bp[j >> 3];
+                const uint32_t bw[4] = {bv.x, bv.y, bv.z, bv.w};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                  const uint32_t u = (bw[e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
+                  const float bf = DT == QZ_DT_F16 ? __half2float(__ushort_as_half((unsigned short)u))
+                                                   : __uint_as_float(u << 16);
+                  v = fmaf(bf, tp[j + e], v);
+                }
+              }
+            }
+            for (; j < r; ++j) v = fmaf(load_f32<DT>(lo->B, (long long)(b0 + j)), tp[j], v);
+          }
+        }
+      }
       store_f32<DT>(p.Y, (long long)c * p.ldy + m, v);
     }
   }
@@ -2315,6 +2354,25 @@ __global__ __launch_bounds__(64 * kMtWaves) void k_gemv_4bit_mt_grouped(GemmGrou
   s = __builtin_amdgcn_readfirstlane(s);
   const GemmParams seg = g.seg[s];
   mt_body<QT, DQ, DT, TB>(seg, b - g.start[s]);
+}
+
+// k_gemv_4bit_mt_grouped with one adapter bank operand per segment (a kernel of its own, so the
+// plain kernels are compiled from exactly the code they had)
+struct MtLoraGroup {
+  MtLora seg[kMtMaxSeg];
+};
+
+template <int QT, bool DQ, int DT, int TB>
+__global__ __launch_bounds__(64 * kMtWaves) void k_gemv_4bit_mt_grouped_lora(GemmGroup g, MtLoraGroup lg) {
+  const int b = blockIdx.x;
+  int s = 0;
+#pragma unroll
+  for (int i = 1; i < kMtMaxSeg; ++i)
+    if (i < g.nseg && b >= g.start[i]) s = i;
+  s = __builtin_amdgcn_readfirstlane(s);
+  const GemmParams seg = g.seg[s];
+  const MtLora lo = lg.seg[s];
+  mt_body<QT, DQ, DT, TB, kMtWaves, true>(seg, b - g.start[s], &lo);
 }
 
 // Y[t, m] = sum_z ws[z][t][m] (+ bias[m]); 4 consecutive m per thread.
@@ -2580,8 +2638,11 @@ extern "C" int qz_gemm_4bit(int T, int M, int K, const void *X, int ldx, int dty
   return QZ_OK;
 }
 
-extern "C" int qz_gemm_4bit_grouped(int nseg, const qz_gemv_segment *segs, int T, int K, const void *X, int ldx,
-                                    int dtype, int quant_type, int blocksize, int blocksize2, void *stream) {
+// qz_gemm_4bit_grouped, and with `lora` (one bank operand per segment) qz_gemm_4bit_grouped_lora:
+// the same checks and declines, the same grid
+static int gemm_grouped_impl(int nseg, const qz_gemv_segment *segs, const qz_lora_bank_segment *lora, const float *t,
+                             int t_stride, const int *slot, int tokens_per_slot, int T, int K, const void *X, int ldx,
+                             int dtype, int quant_type, int blocksize, int blocksize2, void *stream) {
   if (nseg < 1 || nseg > QZ_GEMV_MAX_SEGMENTS || !segs || !X || T < 0 || K < 0) return QZ_ERR_ARG;
   if (quant_type != QZ_FP4 && quant_type != QZ_NF4) return QZ_ERR_DTYPE;
   if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) return QZ_ERR_DTYPE;
@@ -2620,11 +2681,30 @@ extern "C" int qz_gemm_4bit_grouped(int nseg, const qz_gemv_segment *segs, int T
     blocks += (q.M + 15) / 16;
   }
   for (int i = nseg; i < kMtMaxSeg; ++i) g.start[i] = blocks;
+  MtLoraGroup lg{};
+  if (lora) {
+    if (!t || t_stride < 0 || tokens_per_slot < 1) return QZ_ERR_ARG;
+    for (int i = 0; i < nseg; ++i) {
+      const qz_lora_bank_segment &q = lora[i];
+      if (!q.B) continue;
+      if (q.n < 1 || q.n > QZ_LORA_MAX_ADAPTERS || q.r < 1 || q.r > QZ_LORA_MAX_RANK || q.t_offset < 0 ||
+          q.t_offset + q.r > t_stride)
+        return QZ_ERR_ARG;
+      if ((reinterpret_cast<uintptr_t>(q.B) % 16) != 0) return QZ_ERR_SHAPE;
+      lg.seg[i] = MtLora{q.B, t + q.t_offset, slot, q.n, q.r, t_stride, tokens_per_slot};
+    }
+  }
   if (blocks == 0 || T == 0) return QZ_OK;
   hipStream_t s = (hipStream_t)stream;
   const int tb = mt_bucket(T);
-#define QZ_MTGB(QT_, DQ_, DT_, TB_) \
-  hipLaunchKernelGGL((k_gemv_4bit_mt_grouped<QT_, DQ_, DT_, TB_>), dim3(blocks), dim3(64 * kMtWaves), 0, s, g)
+#define QZ_MTGB(QT_, DQ_, DT_, TB_)                                                                                  \
+  do {                                                                                                               \
+    if (lora)                                                                                                        \
+      hipLaunchKernelGGL((k_gemv_4bit_mt_grouped_lora<QT_, DQ_, DT_, TB_>), dim3(blocks), dim3(64 * kMtWaves), 0, s, \
+                         g, lg);                                                                                     \
+    else                                                                                                             \
+      hipLaunchKernelGGL((k_gemv_4bit_mt_grouped<QT_, DQ_, DT_, TB_>), dim3(blocks), dim3(64 * kMtWaves), 0, s, g);  \
+  } while (0)
 #define QZ_MTG(QT_, DQ_, DT_)                                            \
   do {                                                                   \
     if (tb == 2) QZ_MTGB(QT_, DQ_, DT_, 2);                              \
@@ -2644,4 +2724,19 @@ extern "C" int qz_gemm_4bit_grouped(int nseg, const qz_gemv_segment *segs, int T
 #undef QZ_MTGB
   QZ_LAUNCH_CHECK();
   return QZ_OK;
+}
+
+extern "C" int qz_gemm_4bit_grouped(int nseg, const qz_gemv_segment *segs, int T, int K, const void *X, int ldx,
+                                    int dtype, int quant_type, int blocksize, int blocksize2, void *stream) {
+  return gemm_grouped_impl(nseg, segs, nullptr, nullptr, 0, nullptr, 1, T, K, X, ldx, dtype, quant_type, blocksize,
+                           blocksize2, stream);
+}
+
+extern "C" int qz_gemm_4bit_grouped_lora(int nseg, const qz_gemv_segment *segs, const qz_lora_bank_segment *lora,
+                                         const float *t, int t_stride, const int *slot, int tokens_per_slot, int T,
+                                         int K, const void *X, int ldx, int dtype, int quant_type, int blocksize,
+                                         int blocksize2, void *stream) {
+  if (!lora) return QZ_ERR_ARG;
+  return gemm_grouped_impl(nseg, segs, lora, t, t_stride, slot, tokens_per_slot, T, K, X, ldx, dtype, quant_type,
+                           blocksize, blocksize2, stream);
 }

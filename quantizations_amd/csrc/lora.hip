@@ -16,6 +16,9 @@
 //    They are kernels of their own, so the kernels of layers without an adapter are compiled from
 //    exactly the code they had, and scaling (read from device memory by the shrink launch only) is
 //    not baked into a captured graph.
+//  * qz_lora_shrink_mt: the shrink for 2..16 token rows, each row on its own adapter of a bank (or
+//    on none), chosen by a device slot table.  Its expand lives in the multi-token body's epilogue
+//    (gemm.hip: mt_body<..., LORA>, qz_gemm_4bit_grouped_lora).
 #include "gemv_core.h"
 
 namespace qz {
@@ -143,6 +146,78 @@ __global__ __launch_bounds__(256) void k_lora_shrink(ShrinkArgs a) {
   if (tid == 0) {
     const float d = __fadd_rn(__fadd_rn(s_dot[0], s_dot[1]), __fadd_rn(s_dot[2], s_dot[3]));
     a.t[a.t_off[s] + j] = __fmul_rn(scaling, d);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// shrink for 2..16 token rows, each on its own adapter of a bank: t[c] = scaling[a] * A[a] X[c]
+// ---------------------------------------------------------------------------
+
+struct ShrinkMtArgs {
+  const void *A[kMaxSeg];          // bank i: [n, r, K]
+  const float *scaling[kMaxSeg];   // [n]
+  int start[kMaxSeg];              // first workgroup column (= first rank row over all banks) of bank i
+  int t_off[kMaxSeg];
+  int n[kMaxSeg];
+  int r[kMaxSeg];
+  int nseg;
+  int K, ldx, t_stride, S;
+  const void *x;
+  const int *slot;
+  float *t;
+};
+
+// Workgroup (b, c): rank row j of bank s for token row c, on k_lora_shrink's body (thread t takes
+// the 16-B chunks t, t + 256, ... of the row, the first kHeld of them loaded up front; the same
+// butterfly and partial order, so the same summation depth).  The row's adapter a = slot[c / S] is
+// uniform over the workgroup; outside [0, n) the workgroup writes t = 0 and forms no address from a.
+// One workgroup per (rank row, token) and not one per rank row looping over its tokens: the tokens
+// of a batch sit on different adapters, so they share no row of A, and the launch stays one
+// dependent memory round trip deep.
+template <int DT>
+__global__ __launch_bounds__(256) void k_lora_shrink_mt(ShrinkMtArgs a) {
+  constexpr int kHeld = 2;
+  __shared__ float s_dot[4];
+  const int b = blockIdx.x, c = blockIdx.y;
+  int s = 0;
+#pragma unroll
+  for (int i = 1; i < kMaxSeg; ++i)
+    if (i < a.nseg && b >= a.start[i]) s = i;
+  s = __builtin_amdgcn_readfirstlane(s);
+  const int j = b - a.start[s];
+  const int K = a.K, nchunk = K >> 3;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  float *out = a.t + (size_t)c * (size_t)a.t_stride + a.t_off[s] + j;
+  const int ad = a.slot ? a.slot[c / a.S] : 0;
+  if (ad < 0 || ad >= a.n[s]) {   // no adapter for this row
+    if (tid == 0) *out = 0.0f;
+    return;
+  }
+  const u32x4 *xp = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(a.x) + (size_t)c * (size_t)a.ldx * 2u);
+  const u32x4 *ap = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(a.A[s]) +
+                                                    ((size_t)ad * (size_t)a.r[s] + (size_t)j) * (size_t)K * 2u);
+  const float scaling = a.scaling[s][ad];
+
+  u32x4 xh[kHeld], ah[kHeld];
+#pragma unroll
+  for (int i = 0; i < kHeld; ++i) {
+    const int ch = tid + 256 * i;
+    if (ch < nchunk) {
+      xh[i] = xp[ch];
+      ah[i] = ap[ch];
+    }
+  }
+  float acc = 0.0f;
+#pragma unroll
+  for (int i = 0; i < kHeld; ++i)
+    if (tid + 256 * i < nchunk) acc = chunk_dot16<DT>(ah[i], xh[i], acc);
+  for (int ch = tid + 256 * kHeld; ch < nchunk; ch += 256) acc = chunk_dot16<DT>(ap[ch], xp[ch], acc);
+  acc = norm_wave_sum(acc);
+  if (lane == 0) s_dot[wave] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    const float d = __fadd_rn(__fadd_rn(s_dot[0], s_dot[1]), __fadd_rn(s_dot[2], s_dot[3]));
+    *out = __fmul_rn(scaling, d);
   }
 }
 
@@ -386,6 +461,56 @@ extern "C" int qz_lora_shrink(int nseg, const qz_lora_shrink_segment *segs, int 
     if (norm_weight) hipLaunchKernelGGL((k_lora_shrink<QZ_DT_BF16, true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((k_lora_shrink<QZ_DT_BF16, false>), grid, block, 0, s, a);
   }
+  QZ_LAUNCH_CHECK();
+  return QZ_OK;
+}
+
+extern "C" int qz_lora_shrink_mt(int nseg, const qz_lora_bank_shrink_segment *segs, int T, int K, const void *X,
+                                 int ldx, int dtype, const int *slot, int tokens_per_slot, float *t, int t_stride,
+                                 void *stream) {
+  if (nseg < 1 || nseg > QZ_GEMV_MAX_SEGMENTS || !segs || !X || !t || K < 0 || tokens_per_slot < 1 || t_stride < 0)
+    return QZ_ERR_ARG;
+  if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) return QZ_ERR_DTYPE;
+  ShrinkMtArgs a;
+  int blocks = 0;
+  uintptr_t align = (uintptr_t)X;
+  for (int i = 0; i < kMaxSeg; ++i) {
+    if (i < nseg) {
+      const qz_lora_bank_shrink_segment &q = segs[i];
+      if (!q.A || !q.scaling || q.n < 1 || q.n > QZ_LORA_MAX_ADAPTERS || q.r < 1 || q.r > QZ_LORA_MAX_RANK ||
+          q.t_offset < 0 || q.t_offset + q.r > t_stride)
+        return QZ_ERR_ARG;
+      a.A[i] = q.A;
+      a.scaling[i] = q.scaling;
+      a.start[i] = blocks;
+      a.t_off[i] = q.t_offset;
+      a.n[i] = q.n;
+      a.r[i] = q.r;
+      blocks += q.r;
+      align |= (uintptr_t)q.A;
+    } else {
+      a.A[i] = nullptr;
+      a.scaling[i] = nullptr;
+      a.start[i] = blocks;
+      a.t_off[i] = 0;
+      a.n[i] = 0;
+      a.r[i] = 0;
+    }
+  }
+  // 16-B chunks of 8 elements: rows of A and of X start on a chunk when K % 8 == 0 and ldx % 8 == 0
+  if (T < 2 || T > 16 || K == 0 || K % 8 != 0 || ldx < K || ldx % 8 != 0 || align % 16 != 0) return QZ_ERR_SHAPE;
+  a.nseg = nseg;
+  a.K = K;
+  a.ldx = ldx;
+  a.t_stride = t_stride;
+  a.S = tokens_per_slot;
+  a.x = X;
+  a.slot = slot;
+  a.t = t;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)blocks, (unsigned)T), block(256);
+  if (dtype == QZ_DT_F16) hipLaunchKernelGGL((k_lora_shrink_mt<QZ_DT_F16>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((k_lora_shrink_mt<QZ_DT_BF16>), grid, block, 0, s, a);
   QZ_LAUNCH_CHECK();
   return QZ_OK;
 }

@@ -582,15 +582,9 @@ def unfuse_decode_glue(model: nn.Module) -> None:
 _LORA_PREFIX = "base_model.model."
 
 
-def load_lora_adapter(model: nn.Module, path: str) -> int:
-    """Give the Linear4bit layers of `model` the LoRA adapter of a peft adapter directory
-    (``adapter_config.json`` + ``adapter_model.safetensors``; peft itself is not needed).  Keys
-    ``base_model.model.<module path>.lora_A.weight`` / ``....lora_B.weight`` map to
-    ``Linear4bit.set_adapter`` of that module; scaling = lora_alpha / r, or lora_alpha / sqrt(r)
-    with ``use_rslora``, r taken from each layer's tensors (so ``rank_pattern`` works).  DoRA,
-    ``alpha_pattern``, trained biases and ``modules_to_save`` are refused (NotImplementedError
-    naming the field); a key whose module is not a Linear4bit of the model raises KeyError.
-    Returns the number of layers given an adapter."""
+def _read_lora_dir(model: nn.Module, path: str) -> dict:
+    """Parse one peft adapter directory against `model` (the checks and refusals of
+    load_lora_adapter) -> {module name: (A, B, scaling)}; nothing is set."""
     import json
     import math
     import os
@@ -628,18 +622,87 @@ def load_lora_adapter(model: nn.Module, path: str) -> int:
             raise KeyError(f"load_lora_adapter: {name!r} lacks lora_A.weight or lora_B.weight")
         if isinstance(targets, (list, tuple)) and targets and not any(name == t or name.endswith("." + t) for t in targets):
             raise KeyError(f"load_lora_adapter: {name!r} is not among target_modules {list(targets)}")
-    for name, ab in pairs.items():   # every key checked: now set them
+    out = {}
+    for name, ab in pairs.items():
         r = ab["A"].shape[0]
-        modules[name].set_adapter(ab["A"], ab["B"], alpha / math.sqrt(r) if rslora else alpha / r)
-    return len(pairs)
+        out[name] = (ab["A"], ab["B"], alpha / math.sqrt(r) if rslora else alpha / r)
+    return out
+
+
+def load_lora_adapter(model: nn.Module, path: str) -> int:
+    """Give the Linear4bit layers of `model` the LoRA adapter of a peft adapter directory
+    (``adapter_config.json`` + ``adapter_model.safetensors``; peft itself is not needed).  Keys
+    ``base_model.model.<module path>.lora_A.weight`` / ``....lora_B.weight`` map to
+    ``Linear4bit.set_adapter`` of that module; scaling = lora_alpha / r, or lora_alpha / sqrt(r)
+    with ``use_rslora``, r taken from each layer's tensors (so ``rank_pattern`` works).  DoRA,
+    ``alpha_pattern``, trained biases and ``modules_to_save`` are refused (NotImplementedError
+    naming the field); a key whose module is not a Linear4bit of the model raises KeyError.
+    Returns the number of layers given an adapter."""
+    parsed = _read_lora_dir(model, path)
+    modules = dict(model.named_modules())
+    for name, (A, B, scaling) in parsed.items():   # every key checked: now set them
+        modules[name].set_adapter(A, B, scaling)
+    return len(parsed)
+
+
+def load_lora_adapters(model: nn.Module, paths, slots: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Several adapters on one resident base: read every peft adapter directory of `paths` (each
+    through load_lora_adapter's parsing and refusals) and give every Linear4bit that any of them
+    targets an adapter bank (``Linear4bit.set_adapter_bank``) with one entry per path -- a zero entry
+    where that adapter does not target the layer, ranks padded per layer to the layer's largest.
+    Every bank references ONE ``slots`` tensor (int32, core.MT_MAX_TOKENS entries, initialised to -1
+    = no adapter; created on the layers' device unless one is passed): write the adapter index of
+    stream b into ``slots[b]`` before a step -- a captured graph reads it at replay.  Returns
+    ``slots``."""
+    from .core import MT_MAX_TOKENS
+
+    paths = list(paths)
+    if not paths:
+        raise ValueError("load_lora_adapters: no adapter directory given")
+    parsed = [_read_lora_dir(model, p) for p in paths]
+    modules = dict(model.named_modules())
+    names = [n for n in modules if any(n in d for d in parsed)]
+    if slots is None:
+        dev = modules[names[0]].weight.device if names else next(model.parameters()).device
+        slots = torch.full((MT_MAX_TOKENS,), -1, dtype=torch.int32, device=dev)
+    for n in names:
+        if modules[n].adapter is not None:
+            raise ValueError(f"load_lora_adapters: {n!r} carries an adapter (unload_lora_adapter first)")
+    for n in names:
+        modules[n].set_adapter_bank([d.get(n) for d in parsed], slots)
+    return slots
+
+
+def replace_lora_adapter(model: nn.Module, index: int, path: str) -> int:
+    """Overwrite entry `index` of every adapter bank of `model` with the adapter of one peft
+    directory, in place (``AdapterBank.put``: a captured graph serves it on its next replay).  A
+    layer with a bank that the new adapter does not target gets a zero entry; a layer it targets
+    that has no bank raises KeyError, a rank above that layer's bank rank ValueError -- both before
+    anything is written.  Returns the number of banks written."""
+    parsed = _read_lora_dir(model, path)
+    modules = dict(model.named_modules())
+    banks = {n: m.adapter_bank for n, m in modules.items() if isinstance(m, Linear4bit) and m.adapter_bank is not None}
+    for n, (A, _, _) in parsed.items():
+        if n not in banks:
+            raise KeyError(f"replace_lora_adapter: {n!r} has no adapter bank")
+        if A.shape[0] > banks[n].r:
+            raise ValueError(f"replace_lora_adapter: {n!r}: rank {A.shape[0]} exceeds the bank's rank {banks[n].r}")
+    for n, bank in banks.items():
+        if not 0 <= index < bank.n:
+            raise IndexError(f"replace_lora_adapter: entry {index} of {bank.n} ({n!r})")
+    for n, bank in banks.items():
+        bank.put(index, *parsed.get(n, (None, None)))
+    return len(banks)
 
 
 def unload_lora_adapter(model: nn.Module) -> int:
-    """Remove every adapter set by load_lora_adapter / Linear4bit.set_adapter.  Returns how many."""
+    """Remove every adapter set by load_lora_adapter / Linear4bit.set_adapter and every adapter bank
+    (load_lora_adapters / Linear4bit.set_adapter_bank).  Returns how many layers were cleared."""
     n = 0
     for m in model.modules():
-        if isinstance(m, Linear4bit) and m.adapter is not None:
+        if isinstance(m, Linear4bit) and (m.adapter is not None or m.adapter_bank is not None):
             m.clear_adapter()
+            m.clear_adapter_bank()
             n += 1
     return n
 

@@ -90,8 +90,14 @@ def _linear4bit_group_compute(group: DecodeGroup, x: torch.Tensor):
         items.append((m.weight, m.weight.quant_state, bias))
     ads = [m.adapter for m in group.members]
     has_ad = any(a is not None for a in ads)
-    if has_ad and fused_norm and not all(lora.fused_ok(a, xin) for a in ads if a is not None):
-        # an adapter the fused route does not take needs the normalised x for its torch ops
+    banks = [m.adapter_bank for m in group.members]
+    for b in banks:
+        if b is not None:
+            lora.bank_rows(b, x)         # more streams than slots: ValueError
+    if fused_norm and (any(b is not None for b in banks) or
+                       (has_ad and not all(lora.fused_ok(a, xin) for a in ads if a is not None))):
+        # an adapter the fused route does not take (and a bank on one token) needs the normalised x
+        # for its torch ops
         x = norm[2](x)
         xin = m0._input(x)
         fused_norm = False
@@ -105,12 +111,23 @@ def _linear4bit_group_compute(group: DecodeGroup, x: torch.Tensor):
         outs = gemv_4bit_grouped(xin, items, exact_codes=exact_codes_for(m0.compute_dtype),
                                  norm=norm[:2] if fused_norm else None, lora=lo)
     elif grouped_tokens_ok(xin, items):
-        outs = gemm_4bit_grouped(xin, items)
+        # banks that share the first bank's slots: one shrink_mt launch, the expand in the grouped launch
+        first = next((b for b in banks if b is not None), None)
+        fused = [b if b is not None and b.slots is first.slots and lora.bank_fused_ok(b, xin) else None for b in banks]
+        lo = None
+        if any(b is not None for b in fused):
+            t, offs = lora.shrink_mt(xin, fused)
+            lo = (t, [None if b is None else (b.B, o) for b, o in zip(fused, offs)], first.slots,
+                  lora.bank_rows(first, xin)[1])
+            banks = [None if f is not None else b for b, f in zip(banks, fused)]
+        outs = gemm_4bit_grouped(xin, items, lora=lo)
     else:  # shapes the multi-token kernel does not take: each member as it would run alone
         outs = [matmul_4bit(xin, w, bias=b, quant_state=st, exact_codes=exact_codes_for(m0.compute_dtype))
                 for w, st, b in items]
     if has_ad:   # the composed path: torch ops on the members' (normalised) input
         outs = [o if a is None else o + lora.composed_term(a, xin, o.dtype) for o, a in zip(outs, ads)]
+    # banks the fused route did not take: the composed torch form
+    outs = [o if b is None else o + lora.composed_bank_term(b, xin, o.dtype) for o, b in zip(outs, banks)]
     return [o if o.dtype == inp_dtype else o.to(inp_dtype) for o in outs]
 
 
@@ -124,7 +141,8 @@ def linear4bit_silu_pair(group: DecodeGroup, x: torch.Tensor):
     if not (x.is_cuda and x.numel() == x.shape[-1] and x.dtype in (torch.float16, torch.bfloat16)):
         return None
     for m in group.members:
-        if m.weight.quant_state is None or m.adapter is not None:   # adapters: grouped launch + silu_mul
+        # adapters and banks: grouped launch + silu_mul
+        if m.weight.quant_state is None or m.adapter is not None or m.adapter_bank is not None:
             return None
         if not m.compute_type_is_set:
             m.set_compute_type(x)
@@ -165,6 +183,8 @@ class Linear4bit(nn.Linear):
         """Serve base(x) + lora_B(lora_A(x)) * scaling: A = lora_A.weight [r, in], B = lora_B.weight
         [out, r].  A second call with the same shapes and dtypes copies into the existing buffers,
         so a captured graph serves the new adapter on its next replay."""
+        if self.adapter_bank is not None:
+            raise ValueError("set_adapter: the layer carries an adapter bank (clear_adapter_bank first)")
         lora.check_shapes(A, B, self.out_features, self.in_features)
         ad = self.adapter
         if ad is not None and ad.matches(A, B):
@@ -175,11 +195,34 @@ class Linear4bit(nn.Linear):
     def clear_adapter(self) -> None:
         self.__dict__.pop("_qz_adapter", None)
 
+    # -- adapter bank (lora.AdapterBank): several adapters, one per decode stream; like the adapter
+    # it lives in __dict__ (not in state_dict(), kept by deepcopy).  A layer has an adapter OR a bank --
+    @property
+    def adapter_bank(self):
+        """The layer's lora.AdapterBank, or None."""
+        return self.__dict__.get("_qz_adapter_bank")
+
+    def set_adapter_bank(self, adapters, slots) -> None:
+        """Serve base(x_b) + lora_B_a(lora_A_a(x_b)) * scaling_a with a = slots[b] for stream b of x
+        (x [..., S, K]: S consecutive rows per stream; 2-D x: one row per stream); any slots[b]
+        outside [0, len(adapters)) serves the base alone.  adapters: a sequence of (A [r_i, in],
+        B [out, r_i], scaling) or None (an all-zero entry), padded to the largest rank.  slots: an
+        int32 tensor on the layer's device that the caller owns (usually one for the whole model),
+        read on the device at run time; None puts every row on entry 0."""
+        if self.adapter is not None:
+            raise ValueError("set_adapter_bank: the layer carries an adapter (clear_adapter first)")
+        self.__dict__["_qz_adapter_bank"] = lora.AdapterBank(adapters, slots, self.out_features, self.in_features,
+                                                             self.weight.device)
+
+    def clear_adapter_bank(self) -> None:
+        self.__dict__.pop("_qz_adapter_bank", None)
+
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
-        ad = self.adapter
-        if ad is not None and self.weight.device.type != "meta":
-            ad.to(self.weight.device)   # the adapter follows the layer's device
+        if self.weight.device.type != "meta":
+            for ad in (self.adapter, self.adapter_bank):
+                if ad is not None:
+                    ad.to(self.weight.device)   # the adapter / bank follows the layer's device
         return out
 
     def set_compute_type(self, x):
@@ -218,10 +261,21 @@ class Linear4bit(nn.Linear):
             out = gemv_4bit(xin, self.weight, state=qs, bias=bias, exact_codes=exact_codes_for(self.compute_dtype),
                             lora=(ad.B, t))
             return out if out.dtype == inp_dtype else out.to(inp_dtype)
+        bank = self.adapter_bank
+        if bank is not None:
+            _, tps = lora.bank_rows(bank, xin)
+            items = [(self.weight, qs, bias)]
+            if lora.bank_fused_ok(bank, xin) and grouped_tokens_ok(xin, items):
+                # 2..16 rows: shrink_mt, then the multi-token launch carries the expand
+                t, offs = lora.shrink_mt(xin, [bank])
+                out = gemm_4bit_grouped(xin, items, lora=(t, [(bank.B, offs[0])], bank.slots, tps))[0]
+                return out if out.dtype == inp_dtype else out.to(inp_dtype)
         out = matmul_4bit(xin, self.weight, bias=bias, quant_state=qs,
                           exact_codes=exact_codes_for(self.compute_dtype))
         if ad is not None:
             out = out + lora.composed_term(ad, xin, out.dtype)
+        if bank is not None:
+            out = out + lora.composed_bank_term(bank, xin, out.dtype)
         return out if out.dtype == inp_dtype else out.to(inp_dtype)
 
     def forward_residual(self, x: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
@@ -230,6 +284,7 @@ class Linear4bit(nn.Linear):
         add) when x is a single token this layer decodes on its own; otherwise the two ops."""
         qs = self.weight.quant_state
         if (qs is not None and x.is_cuda and x.numel() == x.shape[-1] and self.__dict__.get("_qz_group") is None
+                and self.adapter_bank is None
                 and residual.dtype == x.dtype and residual.device == x.device and residual.is_contiguous()
                 and residual.numel() == qs.shape[0] and residual.shape[:-1] == x.shape[:-1]):
             if not self.compute_type_is_set:

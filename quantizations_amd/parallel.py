@@ -384,6 +384,9 @@ def _refuse_adapter(layer: nn.Module, what: str) -> None:
     if getattr(layer, "adapter", None) is not None:
         raise NotImplementedError(f"{what}: the Linear4bit carries a LoRA adapter; sharded adapters are not "
                                   "implemented (unload_lora_adapter first)")
+    if getattr(layer, "adapter_bank", None) is not None:
+        raise NotImplementedError(f"{what}: the Linear4bit carries a LoRA adapter bank; sharded adapters are not "
+                                  "implemented (unload_lora_adapter first)")
 
 
 def apply_tensor_parallel(model: nn.Module, rank: Optional[int] = None, world_size: Optional[int] = None,

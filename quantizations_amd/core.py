@@ -408,6 +408,40 @@ def exact_codes_for(compute_dtype):
     return True if compute_dtype == torch.float32 else None
 
 
+def _out_shape(A: Tensor, M: int) -> tuple:
+    """Shape of a single-token A's output: A's leading dimensions (all 1), then M."""
+    return (A.shape[0], A.shape[1], M) if A.dim() == 3 else (A.shape[0], M) if A.dim() == 2 else (M,)
+
+
+def _same_format(s0, st) -> bool:
+    """The two weights share K, quant_type, blocksize and scale format (nested, nested blocksize)."""
+    return (st.shape[1] == s0.shape[1] and st.quant_type == s0.quant_type and st.blocksize == s0.blocksize
+            and st.nested == s0.nested and (not st.nested or st.state2.blocksize == s0.state2.blocksize))
+
+
+def _pack_segments(items, dtype, new_out, what):
+    """items = (B, state, bias[, block_base[, out]]) as a GemvSegment array; segment i writes `out` or
+    new_out(M_i) (may be None).  Returns (segments, outputs, the biases passed: kept until the launch)."""
+    segs = (_lib.GemvSegment * len(items))()
+    outs, biases = [], []
+    for i, item in enumerate(items):
+        B, st, bias = item[0], item[1], item[2]
+        block_base = int(item[3]) if len(item) > 3 else 0
+        y = item[4] if len(item) > 4 else None
+        M = st.shape[0]
+        if y is None:
+            y = new_out(M)
+        elif y.numel() != M or not y.is_contiguous() or y.dtype != dtype:
+            raise ValueError(f"{what}: out {i} must be a contiguous {dtype} tensor of {M} elements")
+        if bias is not None and bias.dtype != dtype:
+            bias = bias.to(dtype)
+        am, qam, am2, code2, off, _ = st.scale_args()
+        segs[i] = _lib.GemvSegment(M, ptr(B), am, qam, am2, code2, off, block_base, ptr(bias), ptr(y))
+        outs.append(y)
+        biases.append(bias)
+    return segs, outs, biases
+
+
 def gemv_4bit(A: Tensor, B: Tensor, out: Optional[Tensor] = None, transposed_A=False, transposed_B=False,
               state=None, bias: Optional[Tensor] = None, block_base: int = 0,
               exact_codes: Optional[bool] = None, residual: Optional[Tensor] = None, lora=None) -> Tensor:
@@ -429,33 +463,26 @@ def gemv_4bit(A: Tensor, B: Tensor, out: Optional[Tensor] = None, transposed_A=F
     if A.shape[-1] != K:
         raise ValueError(f"A has {A.shape[-1]} features, the 4-bit weight expects {K}")
     if out is None:
-        shape = (A.shape[0], A.shape[1], M) if A.dim() == 3 else (A.shape[0], M) if A.dim() == 2 else (M,)
-        out = torch.empty(shape, dtype=A.dtype, device=A.device)
+        out = torch.empty(_out_shape(A, M), dtype=A.dtype, device=A.device)
     A = A.contiguous()
     if bias is not None and bias.dtype != A.dtype:
         bias = bias.to(A.dtype)
     if residual is not None and (residual.dtype != A.dtype or residual.numel() != M or not residual.is_contiguous()
                                  or residual.device != A.device):
         raise ValueError(f"gemv_4bit: residual must be a contiguous {A.dtype} tensor of {M} elements")
+    args = (M, K, ptr(A), dtype_code(A.dtype), ptr(B), _gemv_quant_type(state.quant_type, exact_codes, A.dtype),
+            state.blocksize, *state.scale_args(), block_base, 0, ptr(bias))
     if lora is not None:
         lB, t = lora
         if lB.dtype != A.dtype or lB.dim() != 2 or lB.shape[0] != M or not lB.is_contiguous() or \
                 t.dtype != torch.float32 or t.numel() != lB.shape[1] or not t.is_contiguous():
             raise ValueError(f"gemv_4bit: lora must be (B [{M}, r] contiguous {A.dtype}, t fp32 [r])")
-        check(lib.qz_gemv_4bit_lora(M, K, ptr(A), dtype_code(A.dtype), ptr(B),
-                                    _gemv_quant_type(state.quant_type, exact_codes, A.dtype), state.blocksize,
-                                    *state.scale_args(), block_base, 0, ptr(bias), ptr(residual), ptr(lB),
-                                    int(lB.shape[1]), ptr(t), ptr(out), _lib.stream_of(A)), "gemv_4bit(lora)")
-        return out
-    if residual is not None:
-        check(lib.qz_gemv_4bit_residual(M, K, ptr(A), dtype_code(A.dtype), ptr(B),
-                                        _gemv_quant_type(state.quant_type, exact_codes, A.dtype), state.blocksize,
-                                        *state.scale_args(), block_base, 0, ptr(bias), ptr(residual), ptr(out),
-                                        _lib.stream_of(A)), "gemv_4bit(residual)")
-        return out
-    check(lib.qz_gemv_4bit(M, K, ptr(A), dtype_code(A.dtype), ptr(B), _gemv_quant_type(state.quant_type, exact_codes, A.dtype),
-                           state.blocksize, *state.scale_args(), block_base, 0, ptr(bias), ptr(out),
-                           _lib.stream_of(A)), "gemv_4bit")
+        check(lib.qz_gemv_4bit_lora(*args, ptr(residual), ptr(lB), int(lB.shape[1]), ptr(t), ptr(out),
+                                    _lib.stream_of(A)), "gemv_4bit(lora)")
+    elif residual is not None:
+        check(lib.qz_gemv_4bit_residual(*args, ptr(residual), ptr(out), _lib.stream_of(A)), "gemv_4bit(residual)")
+    else:
+        check(lib.qz_gemv_4bit(*args, ptr(out), _lib.stream_of(A)), "gemv_4bit")
     return out
 
 
@@ -475,26 +502,21 @@ def gemv_4bit_pair_silu(A: Tensor, items, exact_codes: Optional[bool] = None, no
         return None
     s0, s1 = items[0][1], items[1][1]
     K = s0.shape[1]
-    if (A.shape[-1] != K or s1.shape != s0.shape or s1.quant_type != s0.quant_type or s1.blocksize != s0.blocksize
-            or s1.nested != s0.nested or (s0.nested and s1.state2.blocksize != s0.state2.blocksize)):
+    if A.shape[-1] != K or s1.shape[0] != s0.shape[0] or not _same_format(s0, s1):
         return None
     A = A.contiguous()
-    M = s0.shape[0]
-    segs = (_lib.GemvSegment * 2)()
-    for i, (B, st, bias, block_base) in enumerate(items):
-        if bias is not None and bias.dtype != A.dtype:
-            bias = bias.to(A.dtype)
-        am, qam, am2, code2, off, _ = st.scale_args()
-        segs[i] = _lib.GemvSegment(M, ptr(B), am, qam, am2, code2, off, int(block_base), ptr(bias), None)
-    shape = (A.shape[0], A.shape[1], M) if A.dim() == 3 else (A.shape[0], M) if A.dim() == 2 else (M,)
-    h = torch.empty(shape, dtype=A.dtype, device=A.device)
+    segs, _, _biases = _pack_segments(items, A.dtype, lambda M: None, "gemv_4bit_pair_silu")
+    h = torch.empty(_out_shape(A, s0.shape[0]), dtype=A.dtype, device=A.device)
     nw, eps = (None, 0.0) if norm is None else norm
     if nw is not None and not (nw.dtype == A.dtype and nw.is_cuda and nw.is_contiguous() and nw.numel() == K):
         return None
     bs2 = int(s0.state2.blocksize) if s0.nested else 0
     qt = _gemv_quant_type(s0.quant_type, exact_codes, A.dtype)
-    rc = lib.qz_gemv_4bit_pair_silu(ctypes.cast(segs, ctypes.c_void_p), K, ptr(A), dtype_code(A.dtype), qt,
-                                    s0.blocksize, bs2, 0, ptr(nw), float(eps), ptr(h), _lib.stream_of(A))
+
+    def launch(x, nw, eps):
+        return lib.qz_gemv_4bit_pair_silu(ctypes.cast(segs, ctypes.c_void_p), K, ptr(x), dtype_code(x.dtype), qt,
+                                          s0.blocksize, bs2, 0, ptr(nw), float(eps), ptr(h), _lib.stream_of(x))
+    rc = launch(A, nw, eps)
     form = "pair" if nw is None else "pair (norm fused)"
     if rc == _lib.QZ_ERR_SHAPE and nw is not None:
         # the fused norm is not taken here (the split pair at K = 8192, or too many workgroups to
@@ -503,8 +525,7 @@ def gemv_4bit_pair_silu(A: Tensor, items, exact_codes: Optional[bool] = None, no
         # wasted and the caller runs its own.)
         from .layer_ops import rms_norm
         A = rms_norm(A, nw, eps).contiguous()
-        rc = lib.qz_gemv_4bit_pair_silu(ctypes.cast(segs, ctypes.c_void_p), K, ptr(A), dtype_code(A.dtype), qt,
-                                        s0.blocksize, bs2, 0, None, 0.0, ptr(h), _lib.stream_of(A))
+        rc = launch(A, None, 0.0)
         form = "norm launch + pair"
     if rc == _lib.QZ_ERR_SHAPE:
         return None
@@ -539,26 +560,11 @@ def gemv_4bit_grouped(A: Tensor, items, exact_codes: Optional[bool] = None, norm
     if A.shape[-1] != K:
         raise ValueError(f"A has {A.shape[-1]} features, the 4-bit weights expect {K}")
     A = A.contiguous()
-    segs = (_lib.GemvSegment * len(items))()
-    outs = []
-    for i, item in enumerate(items):
-        B, st, bias = item[0], item[1], item[2]
-        block_base = int(item[3]) if len(item) > 3 else 0
-        y = item[4] if len(item) > 4 else None
-        if (st.shape[1] != K or st.quant_type != s0.quant_type or st.blocksize != s0.blocksize
-                or st.nested != s0.nested or (st.nested and st.state2.blocksize != s0.state2.blocksize)):
-            raise ValueError("gemv_4bit_grouped: weights must share K, quant_type, blocksize and scale format")
-        M = st.shape[0]
-        if y is None:
-            shape = (A.shape[0], A.shape[1], M) if A.dim() == 3 else (A.shape[0], M) if A.dim() == 2 else (M,)
-            y = torch.empty(shape, dtype=A.dtype, device=A.device)
-        elif y.numel() != M or not y.is_contiguous() or y.dtype != A.dtype:
-            raise ValueError(f"gemv_4bit_grouped: out {i} must be a contiguous {A.dtype} tensor of {M} elements")
-        if bias is not None and bias.dtype != A.dtype:
-            bias = bias.to(A.dtype)
-        am, qam, am2, code2, off, _ = st.scale_args()
-        segs[i] = _lib.GemvSegment(M, ptr(B), am, qam, am2, code2, off, block_base, ptr(bias), ptr(y))
-        outs.append(y)
+    if not all(_same_format(s0, it[1]) for it in items):
+        raise ValueError("gemv_4bit_grouped: weights must share K, quant_type, blocksize and scale format")
+    segs, outs, _biases = _pack_segments(items, A.dtype,
+                                         lambda M: torch.empty(_out_shape(A, M), dtype=A.dtype, device=A.device),
+                                         "gemv_4bit_grouped")
     bs2 = int(s0.state2.blocksize) if s0.nested else 0
     qt = _gemv_quant_type(s0.quant_type, exact_codes, A.dtype)
     segp = ctypes.cast(segs, ctypes.c_void_p)
@@ -724,9 +730,8 @@ def grouped_tokens_ok(A: Tensor, items) -> bool:
             and 1 <= len(items) <= _lib.GEMV_MAX_SEGMENTS and A.dtype in (torch.float16, torch.bfloat16)):
         return False
     s0 = items[0][1]
-    return all(it[1].shape[1] == K and it[1].quant_type == s0.quant_type and it[1].blocksize == s0.blocksize
-               and it[1].blocksize >= 64 and it[1].nested == s0.nested and it[1].shape[0] % 4 == 0
-               and (not it[1].nested or it[1].state2.blocksize == s0.state2.blocksize) for it in items)
+    return s0.shape[1] == K and all(_same_format(s0, it[1]) and it[1].blocksize >= 64 and it[1].shape[0] % 4 == 0
+                                    for it in items)
 
 
 def gemm_4bit_grouped(A: Tensor, items, lora=None) -> list:
@@ -751,18 +756,9 @@ def gemm_4bit_grouped(A: Tensor, items, lora=None) -> list:
     if A2.stride(-1) != 1 or A2.stride(0) % 8 != 0 or A2.data_ptr() % 16 != 0:
         A2 = A2.contiguous()
     T = A2.shape[0]
-    segs = (_lib.GemvSegment * len(items))()
-    outs = []
-    for i, item in enumerate(items):
-        B, st, bias = item[0], item[1], item[2]
-        block_base = int(item[3]) if len(item) > 3 else 0
-        M = st.shape[0]
-        y = torch.empty((T, M), dtype=A.dtype, device=A.device)
-        if bias is not None and bias.dtype != A.dtype:
-            bias = bias.to(A.dtype)
-        am, qam, am2, code2, off, _ = st.scale_args()
-        segs[i] = _lib.GemvSegment(M, ptr(B), am, qam, am2, code2, off, block_base, ptr(bias), ptr(y))
-        outs.append(y)
+    segs, outs, _biases = _pack_segments([it[:4] for it in items], A.dtype,
+                                         lambda M: torch.empty((T, M), dtype=A.dtype, device=A.device),
+                                         "gemm_4bit_grouped")
     s0 = items[0][1]
     bs2 = int(s0.state2.blocksize) if s0.nested else 0
     if lora is not None:
@@ -792,8 +788,8 @@ def gemm_4bit_grouped(A: Tensor, items, lora=None) -> list:
                                             tps, T, K, ptr(A2), A2.stride(0), dtype_code(A.dtype),
                                             _lib.QUANT_TYPES[s0.quant_type], s0.blocksize, bs2, _lib.stream_of(A)),
               "gemm_4bit_grouped(lora)")
-        return [y.reshape(*lead, y.shape[-1]) for y in outs]
-    check(lib.qz_gemm_4bit_grouped(len(items), ctypes.cast(segs, ctypes.c_void_p), T, K, ptr(A2), A2.stride(0),
-                                   dtype_code(A.dtype), _lib.QUANT_TYPES[s0.quant_type], s0.blocksize, bs2,
-                                   _lib.stream_of(A)), "gemm_4bit_grouped")
+    else:
+        check(lib.qz_gemm_4bit_grouped(len(items), ctypes.cast(segs, ctypes.c_void_p), T, K, ptr(A2), A2.stride(0),
+                                       dtype_code(A.dtype), _lib.QUANT_TYPES[s0.quant_type], s0.blocksize, bs2,
+                                       _lib.stream_of(A)), "gemm_4bit_grouped")
     return [y.reshape(*lead, y.shape[-1]) for y in outs]

@@ -39,7 +39,7 @@
 // next-launch prefetch, fp32-code FMA forms, ablation bits) lost on every decode
 // shape and were removed in round 5; DESIGN.md section 4.1 / 11 keeps their numbers
 // and the git history their code.
-#include "gemv_core.h"
+#include "gemv_launch.h"
 
 namespace qz {
 
@@ -67,26 +67,7 @@ Knobs &gemv_knobs() { return g_knobs; }
 static int g_gemm16_sched = env_int("QZ_GEMM16_SCHED", 971);
 int &gemm16_sched() { return g_gemm16_sched; }
 
-template <bool DQ, int DT, int R, int WK, int NW, bool FS, bool CL, bool WT, bool TWO, int STAMP = 0>
-__global__ __launch_bounds__(NW * 64) void k_gemv_4bit(GemvParams p) {
-  gemv_body<DQ, DT, R, WK, NW, FS, CL, WT, false, false, TWO, false, STAMP>(p, blockIdx.x);
-}
-
-template <bool DQ, int DT, int R, int WK, bool FS, bool CL, bool NRM, bool TWO>
-__global__ __launch_bounds__(256) void k_gemv_4bit_grouped(GemvGroup g) {
-  const int b = blockIdx.x;
-  int s = 0;
-#pragma unroll
-  for (int i = 1; i < kMaxSeg; ++i)
-    if (i < g.nseg && b >= g.start[i]) s = i;
-  s = __builtin_amdgcn_readfirstlane(s);
-  // copy the segment out before load_params launders it: loads through a
-  // computed kernarg address are not invariant, so interleaving them with the
-  // laundering asm would serialise them (one s_waitcnt per field)
-  const GemvParams seg = g.seg[s];
-  const int start = g.start[s];
-  gemv_body<DQ, DT, R, WK, 4, FS, CL, false, NRM, false, TWO, false>(seg, b - start);
-}
+// k_gemv_4bit, k_gemv_4bit_grouped, k_gemv_4bit_generic and their launchers: gemv_launch.h
 
 // LlamaMLP's gate/up pair (gemv_body PAIR): one launch computes act_fn(gate_proj(x)) * up_proj(x)
 template <bool DQ, int DT, int R, bool CL, bool NRM, bool TWO, bool PS = false, bool WT = false>
@@ -96,123 +77,16 @@ __global__ __launch_bounds__(256) void k_gemv_4bit_pair(GemvGroup g) {
   gemv_body<DQ, DT, R, 1, 4, true, CL, WT, NRM, true, TWO, PS>(seg, blockIdx.x, g.seg);
 }
 
-// Generic path for shapes the vector kernel does not cover (gemv_core.h gemv_generic_body)
-template <bool DQ, int DT>
-__global__ __launch_bounds__(256) void k_gemv_4bit_generic(GemvParams p, int quant_type) {
-  gemv_generic_body<DQ, DT>(p, quant_type);
-}
-
-// ---------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------
-
-template <bool DQ, int DT, bool FS, bool CL>
-static void launch_vec(const GemvParams &p, int R, int WK, hipStream_t s) {
-  const int RG = 4 / WK;
-  const unsigned grid = (unsigned)((p.M + R * RG - 1) / (R * RG));
-#define QZ_GV(RR, WW, TWO_) \
-  hipLaunchKernelGGL((k_gemv_4bit<DQ, DT, RR, WW, 4, FS, CL, false, (WW == 1 && TWO_)>), dim3(grid), dim3(256), 0, s, p)
-#define QZ_GV_RW(TWO_)                        \
-  do {                                        \
-    if (R == 4 && WK == 2) QZ_GV(4, 2, TWO_); \
-    else if (R == 4) QZ_GV(4, 1, TWO_);       \
-    else if (R == 2) QZ_GV(2, 1, TWO_);       \
-    else if (WK == 1) QZ_GV(1, 1, TWO_);      \
-    else if (WK == 2) QZ_GV(1, 2, TWO_);      \
-    else QZ_GV(1, 4, TWO_);                   \
-  } while (0)
-  if constexpr (FS) {
-    if (two_steps(p.K, WK, true)) { QZ_GV_RW(true); return; }
-  }
-  // exact codes, K >= 14336 (down_proj: 7 or more K-steps per wave): 8-wave workgroups sharing one
-  // 256-B-entry table (conflict-free, v_perm addresses): 4096 x 14336 8.92 -> 8.70 us, 8192 x 28672
-  // (R = 4) 29.2 -> 25.5 us (profiles/r4_gemv_8wave_wide_table.txt); the per-row sums are the same
-  if constexpr (FS && CL && DT == QZ_DT_F16) {
-    if (WK == 1 && (R == 2 || R == 4) && p.K >= 14336 && gemv_knobs().wide8) {
-      const unsigned g8 = (unsigned)((p.M + R * 8 - 1) / (R * 8));
-      if (R == 4) hipLaunchKernelGGL((k_gemv_4bit<DQ, DT, 4, 1, 8, FS, CL, true, false>), dim3(g8), dim3(512), 0, s, p);
-      else hipLaunchKernelGGL((k_gemv_4bit<DQ, DT, 2, 1, 8, FS, CL, true, false>), dim3(g8), dim3(512), 0, s, p);
-      return;
-    }
-  }
-  QZ_GV_RW(false);
-#undef QZ_GV_RW
-#undef QZ_GV
-}
-
-template <bool DQ, bool FS, bool CL>
-static int dispatch_dt(const GemvParams &p, int dtype, int R, int WK, hipStream_t s) {
-  switch (dtype) {
-    case QZ_DT_F16: launch_vec<DQ, QZ_DT_F16, FS, CL>(p, R, WK, s); return QZ_OK;
-    case QZ_DT_BF16:
-      if constexpr (!CL) { launch_vec<DQ, QZ_DT_BF16, FS, false>(p, R, WK, s); return QZ_OK; }
-      break;
-    case QZ_DT_F32:
-      if constexpr (!CL) { launch_vec<DQ, QZ_DT_F32, FS, false>(p, R, WK, s); return QZ_OK; }
-      break;
-  }
-  return QZ_ERR_DTYPE;
-}
-
-template <bool CL>
-static int dispatch_tab(const GemvParams &p, int dtype, bool dq, bool fs, int R, int WK, hipStream_t s) {
-  if (fs) return dq ? dispatch_dt<true, true, CL>(p, dtype, R, WK, s) : dispatch_dt<false, true, CL>(p, dtype, R, WK, s);
-  return dq ? dispatch_dt<true, false, CL>(p, dtype, R, WK, s) : dispatch_dt<false, false, CL>(p, dtype, R, WK, s);
-}
-
 }  // namespace qz
 
 using namespace qz;
-
-static int gemv_impl(int M, int K, const void *x, int dtype, const unsigned char *B, int quant_type, int blocksize,
-                     const float *absmax, const unsigned char *qabsmax, const float *absmax2, const float *code2,
-                     const float *offset, int blocksize2, long long block_base, const float *lut, const void *bias,
-                     const void *res, void *y, void *stream) {
-  GemvParams p;
-  bool vec_ok;
-  const int st = make_params(M, K, x, dtype, B, quant_type, blocksize, absmax, qabsmax, absmax2, code2, offset,
-                             blocksize2, block_base, lut, bias, y, &p, &vec_ok);
-  if (st != QZ_OK) return st;
-  p.res = res;
-  if (M == 0) return QZ_OK;
-  const bool dq = qabsmax != nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  // bf16 x always decodes with bf16 hi + lo codes and fp32 x with fp32 codes: the exact-code (CL)
-  // variant is the fp16-activation option only
-  const bool cl = exact_codes(quant_type, lut) && dtype == QZ_DT_F16;
-  quant_type &= ~QZ_EXACT_CODES;
-
-  if (!vec_ok) {
-    const unsigned grid = (unsigned)((M + 3) / 4);
-    if (K == 0) return QZ_ERR_SHAPE;
-#define QZ_GG(DQ_, DT_) \
-  hipLaunchKernelGGL((k_gemv_4bit_generic<DQ_, DT_>), dim3(grid), dim3(256), 0, s, p, quant_type)
-    if (dq) {
-      if (dtype == QZ_DT_F16) QZ_GG(true, QZ_DT_F16); else if (dtype == QZ_DT_BF16) QZ_GG(true, QZ_DT_BF16); else QZ_GG(true, QZ_DT_F32);
-    } else {
-      if (dtype == QZ_DT_F16) QZ_GG(false, QZ_DT_F16); else if (dtype == QZ_DT_BF16) QZ_GG(false, QZ_DT_BF16); else QZ_GG(false, QZ_DT_F32);
-    }
-#undef QZ_GG
-    QZ_LAUNCH_CHECK();
-    return QZ_OK;
-  }
-
-  int R, WK;
-  choose_geometry(M, K, dtype, &R, &WK);
-  set_tables(quant_type, lut, cl, dtype, &p);
-  const bool fs = full_steps(K, blocksize, blocksize2, dq, block_base);
-  const int rc = cl ? dispatch_tab<true>(p, dtype, dq, fs, R, WK, s) : dispatch_tab<false>(p, dtype, dq, fs, R, WK, s);
-  if (rc != QZ_OK) return rc;
-  QZ_LAUNCH_CHECK();
-  return QZ_OK;
-}
 
 extern "C" int qz_gemv_4bit(int M, int K, const void *x, int dtype, const unsigned char *B, int quant_type,
                             int blocksize, const float *absmax, const unsigned char *qabsmax, const float *absmax2,
                             const float *code2, const float *offset, int blocksize2, long long block_base,
                             const float *lut, const void *bias, void *y, void *stream) {
-  return gemv_impl(M, K, x, dtype, B, quant_type, blocksize, absmax, qabsmax, absmax2, code2, offset, blocksize2,
-                   block_base, lut, bias, nullptr, y, stream);
+  return gemv_impl<false>(M, K, x, dtype, B, quant_type, blocksize, absmax, qabsmax, absmax2, code2, offset,
+                          blocksize2, block_base, lut, bias, nullptr, nullptr, y, stream);
 }
 
 extern "C" int qz_gemv_4bit_residual(int M, int K, const void *x, int dtype, const unsigned char *B, int quant_type,
@@ -221,129 +95,22 @@ extern "C" int qz_gemv_4bit_residual(int M, int K, const void *x, int dtype, con
                                      long long block_base, const float *lut, const void *bias, const void *residual,
                                      void *y, void *stream) {
   if (!residual) return QZ_ERR_ARG;
-  return gemv_impl(M, K, x, dtype, B, quant_type, blocksize, absmax, qabsmax, absmax2, code2, offset, blocksize2,
-                   block_base, lut, bias, residual, y, stream);
-}
-
-// nw != nullptr: x is first RMSNorm'd with weight nw / epsilon eps, bit-identically to qz_rmsnorm
-// (the pre-norm of q/k/v and gate/up fused into their grouped launch)
-static int gemv_grouped_impl(int nseg, const qz_gemv_segment *segs, int K, const void *x, int dtype, int quant_type,
-                             int blocksize, int blocksize2, const float *lut, const void *nw, float eps, void *stream) {
-  if (nseg < 1 || nseg > QZ_GEMV_MAX_SEGMENTS || !segs) return QZ_ERR_ARG;
-  GemvGroup g;
-  g.nseg = nseg;
-  const bool cl = exact_codes(quant_type, lut) && dtype == QZ_DT_F16;
-  bool all_vec = true;
-  long long total_m = 0;
-  const bool dq = segs[0].qabsmax != nullptr;
-  for (int i = 0; i < nseg; ++i) {
-    const qz_gemv_segment &q = segs[i];
-    bool v;
-    const int st = make_params(q.M, K, x, dtype, q.B, quant_type, blocksize, q.absmax, q.qabsmax, q.absmax2, q.code2,
-                               q.offset, blocksize2, q.block_base, lut, q.bias, q.y, &g.seg[i], &v);
-    if (st != QZ_OK) return st;
-    if ((q.qabsmax != nullptr) != dq) return QZ_ERR_ARG;  // one launch = one scale format
-    all_vec = all_vec && v;
-    total_m += q.M;
-  }
-  if (total_m == 0) return QZ_OK;
-  if (nw) {  // the fused pre-norm takes full-step 16-bit single-token launches only
-    if (!all_vec || total_m > INT32_MAX || (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) || K % 8 != 0 || K > 16384 ||
-        ((uintptr_t)x | (uintptr_t)nw) % 16 != 0)
-      return QZ_ERR_SHAPE;
-    for (int i = 0; i < nseg; ++i) {
-      if (!full_steps(K, blocksize, blocksize2, dq, segs[i].block_base)) return QZ_ERR_SHAPE;
-      g.seg[i].nw = nw;
-      g.seg[i].eps = eps;
-    }
-  }
-  if (!all_vec || total_m > INT32_MAX) {  // odd shapes: one launch per segment (same results)
-    for (int i = 0; i < nseg; ++i) {
-      const qz_gemv_segment &q = segs[i];
-      const int rc = qz_gemv_4bit(q.M, K, x, dtype, q.B, quant_type, blocksize, q.absmax, q.qabsmax, q.absmax2,
-                                  q.code2, q.offset, blocksize2, q.block_base, lut, q.bias, q.y, stream);
-      if (rc != QZ_OK) return rc;
-    }
-    return QZ_OK;
-  }
-  int R, WK;
-  choose_geometry((int)total_m, K, dtype, &R, &WK);
-  // QZ_GROUPED_NORM_R (knob): rows per wave of the fused pre-norm launch where the geometry keeps
-  // whole rows per wave (WK = 1: the same per-row sums)
-  if (nw && gemv_knobs().norm_r && WK == 1) R = gemv_knobs().norm_r;
-  const int rows_per_block = R * (4 / WK);
-  int blocks = 0;
-  for (int i = 0; i < nseg; ++i) {
-    set_tables(quant_type & ~QZ_EXACT_CODES, lut, cl, dtype, &g.seg[i]);
-    g.start[i] = blocks;
-    blocks += (g.seg[i].M + rows_per_block - 1) / rows_per_block;
-  }
-  for (int i = nseg; i < kMaxSeg; ++i) g.start[i] = blocks;
-  g.total = blocks;
-  // every workgroup repeats the norm prologue (x and the norm weight from L2, two barriers, 8 KiB
-  // more LDS): past ~4096 workgroups it costs more than the separate launch saves (measured:
-  // Llama-3-70B gate/up, 7168 workgroups, 74.6 us fused vs 58.6 us for the two launches;
-  // profiles/r3_prenorm_launch_times.txt)
-  if (nw && blocks > kNormMaxBlocks) return QZ_ERR_SHAPE;
-  // where K is split over waves and the prologue is large (the Llama-3-70B q/k/v: 1280 workgroups
-  // each normalising 8192 values) the norm launch + the plain grouped launch beat the fused prologue
-  // (16.41 vs 17.23 us, profiles/r5_qkv70_forms.txt): the caller runs the two launches.  A row
-  // shard's q/k/v (Llama-3-8B at N = 8: 384 workgroups x 4096) keeps it fused (round 4's form).
-  if (nw && WK != 1 && (long long)blocks * K > kNormSplitMaxValues) return QZ_ERR_SHAPE;
-  bool all_fs = true;
-  for (int i = 0; i < nseg; ++i) all_fs = all_fs && full_steps(K, blocksize, blocksize2, dq, segs[i].block_base);
-  hipStream_t s = (hipStream_t)stream;
-  const bool two = two_steps(K, WK, all_fs || nw);
-  const size_t lds = nw ? (size_t)K * 2 : 0;
-#define QZ_GR1(DQ_, DT_, RR, WW, FS_, CL_, NRM_)                                                            \
-  do {                                                                                                    \
-    if (FS_ && two && WW == 1)                                                                            \
-      hipLaunchKernelGGL((k_gemv_4bit_grouped<DQ_, DT_, RR, WW, FS_, CL_, NRM_, (FS_ && WW == 1)>), dim3(blocks), \
-                         dim3(256), lds, s, g);                                                           \
-    else hipLaunchKernelGGL((k_gemv_4bit_grouped<DQ_, DT_, RR, WW, FS_, CL_, NRM_, false>), dim3(blocks),      \
-                            dim3(256), lds, s, g);                                                        \
-  } while (0)
-#define QZ_GR_RW(DQ_, DT_, FS_, CL_, NRM_)                                                                  \
-  do {                                                                                                    \
-    if (R == 4 && WK == 2) QZ_GR1(DQ_, DT_, 4, 2, FS_, CL_, NRM_);                                        \
-    else if (R == 4) QZ_GR1(DQ_, DT_, 4, 1, FS_, CL_, NRM_);                                              \
-    else if (R == 2) QZ_GR1(DQ_, DT_, 2, 1, FS_, CL_, NRM_);                                              \
-    else if (WK == 1) QZ_GR1(DQ_, DT_, 1, 1, FS_, CL_, NRM_);                                             \
-    else if (WK == 2) QZ_GR1(DQ_, DT_, 1, 2, FS_, CL_, NRM_);                                             \
-    else QZ_GR1(DQ_, DT_, 1, 4, FS_, CL_, NRM_);                                                          \
-  } while (0)
-#define QZ_GR_DT(DQ_, FS_)                                                                                  \
-  do {                                                                                                    \
-    if (dtype == QZ_DT_F16) { if (cl) QZ_GR_RW(DQ_, QZ_DT_F16, FS_, true, false); else QZ_GR_RW(DQ_, QZ_DT_F16, FS_, false, false); } \
-    else if (dtype == QZ_DT_BF16) QZ_GR_RW(DQ_, QZ_DT_BF16, FS_, false, false);                         \
-    else QZ_GR_RW(DQ_, QZ_DT_F32, FS_, false, false);                                                    \
-  } while (0)
-  if (nw) {
-    if (dtype == QZ_DT_F16) {
-      if (dq) { if (cl) QZ_GR_RW(true, QZ_DT_F16, true, true, true); else QZ_GR_RW(true, QZ_DT_F16, true, false, true); }
-      else { if (cl) QZ_GR_RW(false, QZ_DT_F16, true, true, true); else QZ_GR_RW(false, QZ_DT_F16, true, false, true); }
-    } else {
-      if (dq) QZ_GR_RW(true, QZ_DT_BF16, true, false, true); else QZ_GR_RW(false, QZ_DT_BF16, true, false, true);
-    }
-  } else if (all_fs) { if (dq) QZ_GR_DT(true, true); else QZ_GR_DT(false, true); }
-  else { if (dq) QZ_GR_DT(true, false); else QZ_GR_DT(false, false); }
-#undef QZ_GR_DT
-#undef QZ_GR_RW
-#undef QZ_GR1
-  QZ_LAUNCH_CHECK();
-  return QZ_OK;
+  return gemv_impl<false>(M, K, x, dtype, B, quant_type, blocksize, absmax, qabsmax, absmax2, code2, offset,
+                          blocksize2, block_base, lut, bias, residual, nullptr, y, stream);
 }
 
 extern "C" int qz_gemv_4bit_grouped(int nseg, const qz_gemv_segment *segs, int K, const void *x, int dtype,
                                     int quant_type, int blocksize, int blocksize2, const float *lut, void *stream) {
-  return gemv_grouped_impl(nseg, segs, K, x, dtype, quant_type, blocksize, blocksize2, lut, nullptr, 0.0f, stream);
+  return gemv_grouped_impl<false>(nseg, segs, nullptr, nullptr, K, x, dtype, quant_type, blocksize, blocksize2, lut,
+                                  nullptr, 0.0f, stream);
 }
 
 extern "C" int qz_gemv_4bit_grouped_rmsnorm(int nseg, const qz_gemv_segment *segs, int K, const void *x, int dtype,
                                             int quant_type, int blocksize, int blocksize2, const float *lut,
                                             const void *norm_weight, float eps, void *stream) {
   if (!norm_weight || !x) return QZ_ERR_ARG;
-  return gemv_grouped_impl(nseg, segs, K, x, dtype, quant_type, blocksize, blocksize2, lut, norm_weight, eps, stream);
+  return gemv_grouped_impl<false>(nseg, segs, nullptr, nullptr, K, x, dtype, quant_type, blocksize, blocksize2, lut,
+                                  norm_weight, eps, stream);
 }
 
 // the persistent exact-code pair on the 256-B-entry table (64 KiB: 32 bank-private copies of each 8-B

@@ -15,38 +15,16 @@
 //    row adds B[row][j] * t[j] / out_scale into the row's accumulator before the wave reduction.
 //    They are kernels of their own, so the kernels of layers without an adapter are compiled from
 //    exactly the code they had, and scaling (read from device memory by the shrink launch only) is
-//    not baked into a captured graph.
+//    not baked into a captured graph.  The kernels and their launchers are gemv_launch.h's, shared
+//    with gemv.hip: this file instantiates the LORA side (qz_gemv_4bit_lora,
+//    qz_gemv_4bit_grouped_lora check the adapter operand and call gemv_impl<true> /
+//    gemv_grouped_impl<true>), so the geometry and the fused-norm declines are written once.
 //  * qz_lora_shrink_mt: the shrink for 2..16 token rows, each row on its own adapter of a bank (or
 //    on none), chosen by a device slot table.  Its expand lives in the multi-token body's epilogue
 //    (gemm.hip: mt_body<..., LORA>, qz_gemm_4bit_grouped_lora).
-#include "gemv_core.h"
+#include "gemv_launch.h"
 
 namespace qz {
-
-template <bool DQ, int DT, int R, int WK, int NW, bool FS, bool CL, bool WT, bool TWO>
-__global__ __launch_bounds__(NW * 64) void k_gemv_4bit_lora(GemvParams p, LoraOp l) {
-  gemv_body<DQ, DT, R, WK, NW, FS, CL, WT, false, false, TWO, false, 0, true>(p, blockIdx.x, nullptr, &l);
-}
-
-template <bool DQ, int DT, int R, int WK, bool FS, bool CL, bool NRM, bool TWO>
-__global__ __launch_bounds__(256) void k_gemv_4bit_grouped_lora(GemvGroup g, LoraGroup lg) {
-  const int b = blockIdx.x;
-  int s = 0;
-#pragma unroll
-  for (int i = 1; i < kMaxSeg; ++i)
-    if (i < g.nseg && b >= g.start[i]) s = i;
-  s = __builtin_amdgcn_readfirstlane(s);
-  // copied out before load_params launders them (see k_gemv_4bit_grouped)
-  const GemvParams seg = g.seg[s];
-  const LoraOp lo = lg.seg[s];
-  const int start = g.start[s];
-  gemv_body<DQ, DT, R, WK, 4, FS, CL, false, NRM, false, TWO, false, 0, true>(seg, b - start, nullptr, &lo);
-}
-
-template <bool DQ, int DT>
-__global__ __launch_bounds__(256) void k_gemv_4bit_generic_lora(GemvParams p, int quant_type, LoraOp l) {
-  gemv_generic_body<DQ, DT, true>(p, quant_type, &l);
-}
 
 // ---------------------------------------------------------------------------
 // shrink: t = scaling * A x'
@@ -225,49 +203,31 @@ __global__ __launch_bounds__(256) void k_lora_shrink_mt(ShrinkMtArgs a) {
 // host side
 // ---------------------------------------------------------------------------
 
-// the geometry switch of gemv.hip's launch_vec, on the adapter-carrying kernels
-template <bool DQ, int DT, bool FS, bool CL>
-static void launch_vec_lora(const GemvParams &p, const LoraOp &l, int R, int WK, hipStream_t s) {
-  const int RG = 4 / WK;
-  const unsigned grid = (unsigned)((p.M + R * RG - 1) / (R * RG));
-#define QZ_GV(RR, WW, TWO_)                                                                                      \
-  hipLaunchKernelGGL((k_gemv_4bit_lora<DQ, DT, RR, WW, 4, FS, CL, false, (WW == 1 && TWO_)>), dim3(grid), dim3(256), \
-                     0, s, p, l)
-#define QZ_GV_RW(TWO_)                        \
-  do {                                        \
-    if (R == 4 && WK == 2) QZ_GV(4, 2, TWO_); \
-    else if (R == 4) QZ_GV(4, 1, TWO_);       \
-    else if (R == 2) QZ_GV(2, 1, TWO_);       \
-    else if (WK == 1) QZ_GV(1, 1, TWO_);      \
-    else if (WK == 2) QZ_GV(1, 2, TWO_);      \
-    else QZ_GV(1, 4, TWO_);                   \
-  } while (0)
-  if constexpr (FS) {
-    if (two_steps(p.K, WK, true)) { QZ_GV_RW(true); return; }
-  }
-  // the 8-wave exact-code form of long rows (gemv.hip launch_vec)
-  if constexpr (FS && CL && DT == QZ_DT_F16) {
-    if (WK == 1 && (R == 2 || R == 4) && p.K >= 14336 && gemv_knobs().wide8) {
-      const unsigned g8 = (unsigned)((p.M + R * 8 - 1) / (R * 8));
-      if (R == 4) hipLaunchKernelGGL((k_gemv_4bit_lora<DQ, DT, 4, 1, 8, FS, CL, true, false>), dim3(g8), dim3(512), 0, s, p, l);
-      else hipLaunchKernelGGL((k_gemv_4bit_lora<DQ, DT, 2, 1, 8, FS, CL, true, false>), dim3(g8), dim3(512), 0, s, p, l);
-      return;
-    }
-  }
-  QZ_GV_RW(false);
-#undef QZ_GV_RW
-#undef QZ_GV
-}
-
-template <bool DQ, bool FS>
-static void dispatch_lora(const GemvParams &p, const LoraOp &l, int dtype, bool cl, int R, int WK, hipStream_t s) {
-  if (dtype == QZ_DT_BF16) launch_vec_lora<DQ, QZ_DT_BF16, FS, false>(p, l, R, WK, s);
-  else if (cl) launch_vec_lora<DQ, QZ_DT_F16, FS, true>(p, l, R, WK, s);
-  else launch_vec_lora<DQ, QZ_DT_F16, FS, false>(p, l, R, WK, s);
-}
-
 static bool lora_args_ok(const void *lora_B, int r, const float *t) {
   return lora_B && t && r >= 1 && r <= QZ_LORA_MAX_RANK;
+}
+
+// The segment table both shrink launches share: adapter (or bank) i owns the workgroups (= rank
+// rows) [start[i], start[i] + r_i) and the columns [t_off[i], t_off[i] + r_i) of t; the unused
+// entries are empty.  Returns the number of rank rows, or -1 for a segment that is not valid;
+// *align collects the A pointers.
+template <typename Args, typename Seg>
+static int pack_shrink_segments(int nseg, const Seg *segs, Args *a, uintptr_t *align) {
+  int blocks = 0;
+  for (int i = 0; i < kMaxSeg; ++i) {
+    const bool on = i < nseg;
+    if (on && (!segs[i].A || !segs[i].scaling || segs[i].r < 1 || segs[i].r > QZ_LORA_MAX_RANK || segs[i].t_offset < 0))
+      return -1;
+    a->A[i] = on ? segs[i].A : nullptr;
+    a->scaling[i] = on ? segs[i].scaling : nullptr;
+    a->start[i] = blocks;
+    a->t_off[i] = on ? segs[i].t_offset : 0;
+    if (on) {
+      blocks += segs[i].r;
+      *align |= (uintptr_t)segs[i].A;
+    }
+  }
+  return blocks;
 }
 
 }  // namespace qz
@@ -281,143 +241,20 @@ extern "C" int qz_gemv_4bit_lora(int M, int K, const void *x, int dtype, const u
                                  const void *lora_B, int r, const float *t, void *y, void *stream) {
   if (!lora_args_ok(lora_B, r, t)) return QZ_ERR_ARG;
   if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) return QZ_ERR_DTYPE;
-  GemvParams p;
-  bool vec_ok;
-  const int st = make_params(M, K, x, dtype, B, quant_type, blocksize, absmax, qabsmax, absmax2, code2, offset,
-                             blocksize2, block_base, lut, bias, y, &p, &vec_ok);
-  if (st != QZ_OK) return st;
-  p.res = residual;
-  if (M == 0) return QZ_OK;
   const LoraOp l{lora_B, t, r};
-  const bool dq = qabsmax != nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  const bool cl = exact_codes(quant_type, lut) && dtype == QZ_DT_F16;
-  quant_type &= ~QZ_EXACT_CODES;
-  if (!vec_ok) {
-    const unsigned grid = (unsigned)((M + 3) / 4);
-    if (K == 0) return QZ_ERR_SHAPE;
-#define QZ_GG(DQ_, DT_) \
-  hipLaunchKernelGGL((k_gemv_4bit_generic_lora<DQ_, DT_>), dim3(grid), dim3(256), 0, s, p, quant_type, l)
-    if (dq) { if (dtype == QZ_DT_F16) QZ_GG(true, QZ_DT_F16); else QZ_GG(true, QZ_DT_BF16); }
-    else { if (dtype == QZ_DT_F16) QZ_GG(false, QZ_DT_F16); else QZ_GG(false, QZ_DT_BF16); }
-#undef QZ_GG
-    QZ_LAUNCH_CHECK();
-    return QZ_OK;
-  }
-  int R, WK;
-  choose_geometry(M, K, dtype, &R, &WK);
-  set_tables(quant_type, lut, cl, dtype, &p);
-  const bool fs = full_steps(K, blocksize, blocksize2, dq, block_base);
-  if (fs) { if (dq) dispatch_lora<true, true>(p, l, dtype, cl, R, WK, s); else dispatch_lora<false, true>(p, l, dtype, cl, R, WK, s); }
-  else { if (dq) dispatch_lora<true, false>(p, l, dtype, cl, R, WK, s); else dispatch_lora<false, false>(p, l, dtype, cl, R, WK, s); }
-  QZ_LAUNCH_CHECK();
-  return QZ_OK;
+  return gemv_impl<true>(M, K, x, dtype, B, quant_type, blocksize, absmax, qabsmax, absmax2, code2, offset,
+                         blocksize2, block_base, lut, bias, residual, &l, y, stream);
 }
 
-// qz_gemv_4bit_grouped(_rmsnorm) with an adapter operand per segment (gemv.hip gemv_grouped_impl:
-// the same checks, geometry and declines)
+// qz_gemv_4bit_grouped(_rmsnorm) with an adapter operand per segment
 extern "C" int qz_gemv_4bit_grouped_lora(int nseg, const qz_gemv_segment *segs, const qz_lora_segment *lora,
                                          const float *t, int K, const void *x, int dtype, int quant_type,
                                          int blocksize, int blocksize2, const float *lut, const void *nw, float eps,
                                          void *stream) {
   if (nseg < 1 || nseg > QZ_GEMV_MAX_SEGMENTS || !segs || !lora || !t) return QZ_ERR_ARG;
   if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) return QZ_ERR_DTYPE;
-  GemvGroup g;
-  LoraGroup lg;
-  g.nseg = nseg;
-  const bool cl = exact_codes(quant_type, lut) && dtype == QZ_DT_F16;
-  bool all_vec = true;
-  long long total_m = 0;
-  const bool dq = segs[0].qabsmax != nullptr;
-  for (int i = 0; i < nseg; ++i) {
-    const qz_gemv_segment &q = segs[i];
-    bool v;
-    const int st = make_params(q.M, K, x, dtype, q.B, quant_type, blocksize, q.absmax, q.qabsmax, q.absmax2, q.code2,
-                               q.offset, blocksize2, q.block_base, lut, q.bias, q.y, &g.seg[i], &v);
-    if (st != QZ_OK) return st;
-    if ((q.qabsmax != nullptr) != dq) return QZ_ERR_ARG;
-    if (lora[i].B) {
-      if (lora[i].r < 1 || lora[i].r > QZ_LORA_MAX_RANK || lora[i].t_offset < 0) return QZ_ERR_ARG;
-      lg.seg[i] = LoraOp{lora[i].B, t + lora[i].t_offset, lora[i].r};
-    } else {
-      lg.seg[i] = LoraOp{t, t, 0};   // no adapter: rank 0, the (unused) loads read t[0]
-    }
-    all_vec = all_vec && v;
-    total_m += q.M;
-  }
-  for (int i = nseg; i < kMaxSeg; ++i) lg.seg[i] = LoraOp{t, t, 0};
-  if (total_m == 0) return QZ_OK;
-  if (nw) {
-    if (!x || !all_vec || total_m > INT32_MAX || K % 8 != 0 || K > 16384 || ((uintptr_t)x | (uintptr_t)nw) % 16 != 0)
-      return QZ_ERR_SHAPE;
-    for (int i = 0; i < nseg; ++i) {
-      if (!full_steps(K, blocksize, blocksize2, dq, segs[i].block_base)) return QZ_ERR_SHAPE;
-      g.seg[i].nw = nw;
-      g.seg[i].eps = eps;
-    }
-  }
-  if (!all_vec || total_m > INT32_MAX) {  // odd shapes: one launch per segment (same results)
-    for (int i = 0; i < nseg; ++i) {
-      const qz_gemv_segment &q = segs[i];
-      const int rc = lora[i].B
-          ? qz_gemv_4bit_lora(q.M, K, x, dtype, q.B, quant_type, blocksize, q.absmax, q.qabsmax, q.absmax2, q.code2,
-                              q.offset, blocksize2, q.block_base, lut, q.bias, nullptr, lora[i].B, lora[i].r,
-                              t + lora[i].t_offset, q.y, stream)
-          : qz_gemv_4bit(q.M, K, x, dtype, q.B, quant_type, blocksize, q.absmax, q.qabsmax, q.absmax2, q.code2,
-                         q.offset, blocksize2, q.block_base, lut, q.bias, q.y, stream);
-      if (rc != QZ_OK) return rc;
-    }
-    return QZ_OK;
-  }
-  int R, WK;
-  choose_geometry((int)total_m, K, dtype, &R, &WK);
-  if (nw && gemv_knobs().norm_r && WK == 1) R = gemv_knobs().norm_r;
-  const int rows_per_block = R * (4 / WK);
-  int blocks = 0;
-  for (int i = 0; i < nseg; ++i) {
-    set_tables(quant_type & ~QZ_EXACT_CODES, lut, cl, dtype, &g.seg[i]);
-    g.start[i] = blocks;
-    blocks += (g.seg[i].M + rows_per_block - 1) / rows_per_block;
-  }
-  for (int i = nseg; i < kMaxSeg; ++i) g.start[i] = blocks;
-  g.total = blocks;
-  if (nw && blocks > kNormMaxBlocks) return QZ_ERR_SHAPE;
-  if (nw && WK != 1 && (long long)blocks * K > kNormSplitMaxValues) return QZ_ERR_SHAPE;
-  bool all_fs = true;
-  for (int i = 0; i < nseg; ++i) all_fs = all_fs && full_steps(K, blocksize, blocksize2, dq, segs[i].block_base);
-  hipStream_t s = (hipStream_t)stream;
-  const bool two = two_steps(K, WK, all_fs || nw);
-  const size_t lds = nw ? (size_t)K * 2 : 0;
-#define QZ_GR1(DQ_, DT_, RR, WW, FS_, CL_, NRM_)                                                                   \
-  do {                                                                                                           \
-    if (FS_ && two && WW == 1)                                                                                   \
-      hipLaunchKernelGGL((k_gemv_4bit_grouped_lora<DQ_, DT_, RR, WW, FS_, CL_, NRM_, (FS_ && WW == 1)>), dim3(blocks), \
-                         dim3(256), lds, s, g, lg);                                                              \
-    else hipLaunchKernelGGL((k_gemv_4bit_grouped_lora<DQ_, DT_, RR, WW, FS_, CL_, NRM_, false>), dim3(blocks),        \
-                            dim3(256), lds, s, g, lg);                                                           \
-  } while (0)
-#define QZ_GR_RW(DQ_, DT_, FS_, CL_, NRM_)                         \
-  do {                                                           \
-    if (R == 4 && WK == 2) QZ_GR1(DQ_, DT_, 4, 2, FS_, CL_, NRM_); \
-    else if (R == 4) QZ_GR1(DQ_, DT_, 4, 1, FS_, CL_, NRM_);       \
-    else if (R == 2) QZ_GR1(DQ_, DT_, 2, 1, FS_, CL_, NRM_);       \
-    else if (WK == 1) QZ_GR1(DQ_, DT_, 1, 1, FS_, CL_, NRM_);      \
-    else if (WK == 2) QZ_GR1(DQ_, DT_, 1, 2, FS_, CL_, NRM_);      \
-    else QZ_GR1(DQ_, DT_, 1, 4, FS_, CL_, NRM_);                   \
-  } while (0)
-#define QZ_GR_DT(DQ_, FS_, NRM_)                                                                                      \
-  do {                                                                                                              \
-    if (dtype == QZ_DT_F16) { if (cl) QZ_GR_RW(DQ_, QZ_DT_F16, FS_, true, NRM_); else QZ_GR_RW(DQ_, QZ_DT_F16, FS_, false, NRM_); } \
-    else QZ_GR_RW(DQ_, QZ_DT_BF16, FS_, false, NRM_);                                                              \
-  } while (0)
-  if (nw) { if (dq) QZ_GR_DT(true, true, true); else QZ_GR_DT(false, true, true); }
-  else if (all_fs) { if (dq) QZ_GR_DT(true, true, false); else QZ_GR_DT(false, true, false); }
-  else { if (dq) QZ_GR_DT(true, false, false); else QZ_GR_DT(false, false, false); }
-#undef QZ_GR_DT
-#undef QZ_GR_RW
-#undef QZ_GR1
-  QZ_LAUNCH_CHECK();
-  return QZ_OK;
+  return gemv_grouped_impl<true>(nseg, segs, lora, t, K, x, dtype, quant_type, blocksize, blocksize2, lut, nw, eps,
+                                 stream);
 }
 
 extern "C" int qz_lora_shrink(int nseg, const qz_lora_shrink_segment *segs, int K, const void *x, int dtype,
@@ -425,25 +262,9 @@ extern "C" int qz_lora_shrink(int nseg, const qz_lora_shrink_segment *segs, int 
   if (nseg < 1 || nseg > QZ_GEMV_MAX_SEGMENTS || !segs || !x || !t || K < 0) return QZ_ERR_ARG;
   if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) return QZ_ERR_DTYPE;
   ShrinkArgs a;
-  int blocks = 0;
   uintptr_t align = (uintptr_t)x | (uintptr_t)norm_weight;
-  for (int i = 0; i < kMaxSeg; ++i) {
-    if (i < nseg) {
-      const qz_lora_shrink_segment &q = segs[i];
-      if (!q.A || !q.scaling || q.r < 1 || q.r > QZ_LORA_MAX_RANK || q.t_offset < 0) return QZ_ERR_ARG;
-      a.A[i] = q.A;
-      a.scaling[i] = q.scaling;
-      a.start[i] = blocks;
-      a.t_off[i] = q.t_offset;
-      blocks += q.r;
-      align |= (uintptr_t)q.A;
-    } else {
-      a.A[i] = nullptr;
-      a.scaling[i] = nullptr;
-      a.start[i] = blocks;
-      a.t_off[i] = 0;
-    }
-  }
+  const int blocks = pack_shrink_segments(nseg, segs, &a, &align);
+  if (blocks < 0) return QZ_ERR_ARG;
   // 16-B chunks of 8 elements: rows of A start on a chunk when K % 8 == 0
   if (K == 0 || K % 8 != 0 || align % 16 != 0) return QZ_ERR_SHAPE;
   a.nseg = nseg;
@@ -472,30 +293,14 @@ extern "C" int qz_lora_shrink_mt(int nseg, const qz_lora_bank_shrink_segment *se
     return QZ_ERR_ARG;
   if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) return QZ_ERR_DTYPE;
   ShrinkMtArgs a;
-  int blocks = 0;
   uintptr_t align = (uintptr_t)X;
+  const int blocks = pack_shrink_segments(nseg, segs, &a, &align);
+  if (blocks < 0) return QZ_ERR_ARG;
   for (int i = 0; i < kMaxSeg; ++i) {
-    if (i < nseg) {
-      const qz_lora_bank_shrink_segment &q = segs[i];
-      if (!q.A || !q.scaling || q.n < 1 || q.n > QZ_LORA_MAX_ADAPTERS || q.r < 1 || q.r > QZ_LORA_MAX_RANK ||
-          q.t_offset < 0 || q.t_offset + q.r > t_stride)
-        return QZ_ERR_ARG;
-      a.A[i] = q.A;
-      a.scaling[i] = q.scaling;
-      a.start[i] = blocks;
-      a.t_off[i] = q.t_offset;
-      a.n[i] = q.n;
-      a.r[i] = q.r;
-      blocks += q.r;
-      align |= (uintptr_t)q.A;
-    } else {
-      a.A[i] = nullptr;
-      a.scaling[i] = nullptr;
-      a.start[i] = blocks;
-      a.t_off[i] = 0;
-      a.n[i] = 0;
-      a.r[i] = 0;
-    }
+    a.n[i] = i < nseg ? segs[i].n : 0;
+    a.r[i] = i < nseg ? segs[i].r : 0;
+    if (i < nseg && (a.n[i] < 1 || a.n[i] > QZ_LORA_MAX_ADAPTERS || segs[i].t_offset + a.r[i] > t_stride))
+      return QZ_ERR_ARG;
   }
   // 16-B chunks of 8 elements: rows of A and of X start on a chunk when K % 8 == 0 and ldx % 8 == 0
   if (T < 2 || T > 16 || K == 0 || K % 8 != 0 || ldx < K || ldx % 8 != 0 || align % 16 != 0) return QZ_ERR_SHAPE;

@@ -29,6 +29,11 @@ def matmul_4bit(A: torch.Tensor, B: torch.Tensor, quant_state: QuantState, out: 
     return gemm_4bit(A, B, quant_state, bias=bias)
 
 
+def _as_dtype(out: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """The reference returns the input's dtype (modules.py:149): cast back where compute_dtype differs."""
+    return out if out.dtype == dtype else out.to(dtype)
+
+
 class DecodeGroup:
     """Linear4bit layers that read the same input (q/k/v or gate/up of one
     decoder layer), fused for decode into one grouped launch (SURVEY.md 8f
@@ -84,18 +89,16 @@ def _linear4bit_group_compute(group: DecodeGroup, x: torch.Tensor):
     if norm is not None and not fused_norm:
         x = norm[2](x)                   # the absorbed RMSNorm as its own launch
     xin = m0._input(x)
-    items = []
-    for m in group.members:
-        bias = None if m.bias is None else m.bias.to(xin.dtype)
-        items.append((m.weight, m.weight.quant_state, bias))
+    items = [(m.weight, m.weight.quant_state, None if m.bias is None else m.bias.to(xin.dtype)) for m in group.members]
     ads = [m.adapter for m in group.members]
     has_ad = any(a is not None for a in ads)
+    # every adapter takes the fused route (fused_ok reads x's shape, dtype, device: the norm keeps them)
+    ads_fused = has_ad and all(lora.fused_ok(a, xin) for a in ads if a is not None)
     banks = [m.adapter_bank for m in group.members]
     for b in banks:
         if b is not None:
             lora.bank_rows(b, x)         # more streams than slots: ValueError
-    if fused_norm and (any(b is not None for b in banks) or
-                       (has_ad and not all(lora.fused_ok(a, xin) for a in ads if a is not None))):
+    if fused_norm and (any(b is not None for b in banks) or (has_ad and not ads_fused)):
         # an adapter the fused route does not take (and a bank on one token) needs the normalised x
         # for its torch ops
         x = norm[2](x)
@@ -103,7 +106,7 @@ def _linear4bit_group_compute(group: DecodeGroup, x: torch.Tensor):
         fused_norm = False
     if xin.numel() == xin.shape[-1]:
         lo = None
-        if has_ad and all(lora.fused_ok(a, xin) for a in ads if a is not None):
+        if ads_fused:
             # one shrink launch for all of the group's adapters, then the grouped launch carries B . t
             t, offs = lora.shrink(xin, ads, norm=norm[:2] if fused_norm else None)
             lo = (t, [None if a is None else (a.B, o) for a, o in zip(ads, offs)])
@@ -128,7 +131,7 @@ def _linear4bit_group_compute(group: DecodeGroup, x: torch.Tensor):
         outs = [o if a is None else o + lora.composed_term(a, xin, o.dtype) for o, a in zip(outs, ads)]
     # banks the fused route did not take: the composed torch form
     outs = [o if b is None else o + lora.composed_bank_term(b, xin, o.dtype) for o, b in zip(outs, banks)]
-    return [o if o.dtype == inp_dtype else o.to(inp_dtype) for o in outs]
+    return [_as_dtype(o, inp_dtype) for o in outs]
 
 
 def linear4bit_silu_pair(group: DecodeGroup, x: torch.Tensor):
@@ -144,9 +147,7 @@ def linear4bit_silu_pair(group: DecodeGroup, x: torch.Tensor):
         # adapters and banks: grouped launch + silu_mul
         if m.weight.quant_state is None or m.adapter is not None or m.adapter_bank is not None:
             return None
-        if not m.compute_type_is_set:
-            m.set_compute_type(x)
-            m.compute_type_is_set = True
+        m._set_compute_type_once(x)
     m0, m1 = group.members
     if m0._input(x) is not x or m1._input(x) is not x or \
             exact_codes_for(m0.compute_dtype) != exact_codes_for(m1.compute_dtype):
@@ -230,6 +231,12 @@ class Linear4bit(nn.Linear):
         if x.dtype in [torch.float32, torch.bfloat16]:
             self.compute_dtype = x.dtype
 
+    def _set_compute_type_once(self, x):
+        """The layer's first input sets the compute type (reference modules.py:136-138)."""
+        if not self.compute_type_is_set:
+            self.set_compute_type(x)
+            self.compute_type_is_set = True
+
     def _input(self, x: torch.Tensor) -> torch.Tensor:
         # The reference casts x to compute_dtype before the matmul (modules.py:141-142).
         # Our kernels always accumulate in fp32, so an up-cast (e.g. fp16 -> fp32) is
@@ -241,9 +248,7 @@ class Linear4bit(nn.Linear):
         return x.to(cd)
 
     def forward(self, x: torch.Tensor):
-        if not self.compute_type_is_set:
-            self.set_compute_type(x)
-            self.compute_type_is_set = True
+        self._set_compute_type_once(x)
         qs = self.weight.quant_state
         if qs is None:
             raise RuntimeError("Linear4bit weight is not quantised yet: move the module to a GPU first")
@@ -258,9 +263,8 @@ class Linear4bit(nn.Linear):
         ad = self.adapter
         if ad is not None and lora.fused_ok(ad, xin):   # one token: shrink, then the GEMV carries B . t
             t, _ = lora.shrink(xin, [ad])
-            out = gemv_4bit(xin, self.weight, state=qs, bias=bias, exact_codes=exact_codes_for(self.compute_dtype),
-                            lora=(ad.B, t))
-            return out if out.dtype == inp_dtype else out.to(inp_dtype)
+            return _as_dtype(gemv_4bit(xin, self.weight, state=qs, bias=bias, lora=(ad.B, t),
+                                       exact_codes=exact_codes_for(self.compute_dtype)), inp_dtype)
         bank = self.adapter_bank
         if bank is not None:
             _, tps = lora.bank_rows(bank, xin)
@@ -269,14 +273,14 @@ class Linear4bit(nn.Linear):
                 # 2..16 rows: shrink_mt, then the multi-token launch carries the expand
                 t, offs = lora.shrink_mt(xin, [bank])
                 out = gemm_4bit_grouped(xin, items, lora=(t, [(bank.B, offs[0])], bank.slots, tps))[0]
-                return out if out.dtype == inp_dtype else out.to(inp_dtype)
+                return _as_dtype(out, inp_dtype)
         out = matmul_4bit(xin, self.weight, bias=bias, quant_state=qs,
                           exact_codes=exact_codes_for(self.compute_dtype))
         if ad is not None:
             out = out + lora.composed_term(ad, xin, out.dtype)
         if bank is not None:
             out = out + lora.composed_bank_term(bank, xin, out.dtype)
-        return out if out.dtype == inp_dtype else out.to(inp_dtype)
+        return _as_dtype(out, inp_dtype)
 
     def forward_residual(self, x: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
         """residual + self(x) -- LlamaDecoderLayer's `residual + h` after o_proj / down_proj --
@@ -287,9 +291,7 @@ class Linear4bit(nn.Linear):
                 and self.adapter_bank is None
                 and residual.dtype == x.dtype and residual.device == x.device and residual.is_contiguous()
                 and residual.numel() == qs.shape[0] and residual.shape[:-1] == x.shape[:-1]):
-            if not self.compute_type_is_set:
-                self.set_compute_type(x)
-                self.compute_type_is_set = True
+            self._set_compute_type_once(x)
             ad = self.adapter
             if self._input(x) is x and (ad is None or lora.fused_ok(ad, x)):
                 bias = None if self.bias is None else self.bias.to(x.dtype)

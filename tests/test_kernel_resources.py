@@ -27,27 +27,32 @@ def _tools_ok():
                                                                     "llvm-readelf")))
 
 
+def code_objects(lib, d):
+    """Unbundles the library's gfx950 code objects into directory d; yields their paths."""
+    fat = os.path.join(d, "fat.bin")
+    subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", lib, os.devnull],
+                   check=True, capture_output=True)
+    blob = open(fat, "rb").read()
+    starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
+    for i, st in enumerate(starts):
+        en = starts[i + 1] if i + 1 < len(starts) else len(blob)
+        b, co = os.path.join(d, f"b{i}.bin"), os.path.join(d, f"co{i}.o")
+        with open(b, "wb") as f:
+            f.write(blob[st:en])
+        r = subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o",
+                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={b}", f"--output={co}",
+                            "--unbundle"], capture_output=True)
+        if r.returncode == 0 and os.path.getsize(co):
+            yield co
+
+
 def kernel_resources(lib=LIB):
     """{demangled kernel name: (vgpr_count, agpr_count, private_segment_fixed_size, sgpr_spill_count,
     vgpr_spill_count)} for every gfx950 kernel in the library's offload bundles."""
     out = {}
     with tempfile.TemporaryDirectory() as d:
-        fat = os.path.join(d, "fat.bin")
-        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", lib, os.devnull],
-                       check=True, capture_output=True)
-        blob = open(fat, "rb").read()
-        starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
         names = []
-        for i, st in enumerate(starts):
-            en = starts[i + 1] if i + 1 < len(starts) else len(blob)
-            b, co = os.path.join(d, f"b{i}.bin"), os.path.join(d, f"co{i}.o")
-            with open(b, "wb") as f:
-                f.write(blob[st:en])
-            r = subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o",
-                                "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={b}", f"--output={co}",
-                                "--unbundle"], capture_output=True)
-            if r.returncode != 0 or not os.path.getsize(co):
-                continue
+        for co in code_objects(lib, d):
             notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True,
                                    text=True, check=True).stdout
             for ent in notes.split("  - .agpr_count:")[1:]:

@@ -1,4 +1,4 @@
-// decode.h -- shared 4-bit decode helpers for the fused GEMM (gemm.hip) and
+// decode.h -- shared 4-bit decode helpers for the fused GEMM (gemm_4bit.hip, gemm_mt.hip) and
 // the full-weight dequantiser (dequantize.hip): the per-(row, block) table of
 // exact 16-bit weights fp16/bf16(code[i] * absmax) and the AND-combined
 // v_perm nibble lookup through it (see decode_lut16 in gemv.hip).

@@ -61,7 +61,7 @@ static Knobs read_knobs() {
 }
 static Knobs g_knobs = read_knobs();   // at library load
 Knobs &gemv_knobs() { return g_knobs; }
-// QZ_GEMM16_SCHED: the k_gemm16_4d / k_gemm16_4q schedule qz_gemm_16bit launches (gemm.hip); 971 =
+// QZ_GEMM16_SCHED: the k_gemm16_4d / k_gemm16_4q schedule qz_gemm_16bit launches (gemm_16bit.hip); 971 =
 // the persistent asm-step form with the library's dual event order, W's fragments read and refilled
 // first, non-temporal output stores: the fastest measured (all bit-identical)
 static int g_gemm16_sched = env_int("QZ_GEMM16_SCHED", 971);

@@ -21,7 +21,7 @@
 //    gemv_grouped_impl<true>), so the geometry and the fused-norm declines are written once.
 //  * qz_lora_shrink_mt: the shrink for 2..16 token rows, each row on its own adapter of a bank (or
 //    on none), chosen by a device slot table.  Its expand lives in the multi-token body's epilogue
-//    (gemm.hip: mt_body<..., LORA>, qz_gemm_4bit_grouped_lora).
+//    (gemm_mt.hip: mt_body<..., LORA>, qz_gemm_4bit_grouped_lora).
 #include "gemv_launch.h"
 
 namespace qz {

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 kernels of two builds of a library, per kernel symbol:
 
-    python scripts/dev/compare_kernels.py OLD.so NEW.so
+    python scripts/dev/compare_kernels.py [--rename PATTERN REPL]... OLD.so NEW.so
 
 For every kernel of the two libraries' code objects: the set of names, the kernel's metadata entry
 (registers, LDS, scratch, spills, kernarg layout: the whole amdhsa.kernels record) and its machine
@@ -10,6 +10,9 @@ and the literal of each pc-relative address pair (s_getpc_b64 ... s_add_u32 / s_
 kernel that differs only there addresses the same constant table at another distance because the
 object's layout moved.  Prints counts per kernel family and every difference; exit status 1 if a
 kernel was added, removed or differs otherwise.  A refactor of host code must print zero differences.
+--rename applies re.sub(PATTERN, REPL) to OLD's demangled names first, for a refactor that changed a
+kernel's template parameter list; the metadata records are then compared without their .name and
+.symbol fields (the mangled names), which differ for a renamed kernel by construction.
 """
 import collections
 import os
@@ -66,7 +69,7 @@ def _disassembly(co):
     return out
 
 
-def kernels(lib):
+def kernels(lib, drop_names=False):
     """{demangled name: (metadata record, code bytes, normalised disassembly)}"""
     out = {}
     with tempfile.TemporaryDirectory() as d:
@@ -77,6 +80,8 @@ def kernels(lib):
             for ent in notes.split("  - .agpr_count:")[1:]:
                 sym = re.search(r"\.name:\s+(\S+)", ent).group(1)
                 ent = ent.split("amdhsa.target:")[0]
+                if drop_names:   # a renamed kernel's record differs in its own mangled names by construction
+                    ent = re.sub(r"\.(name|symbol):\s+\S+", "", ent)
                 out[sym] = (ent, code[sym], dis.get(sym, []))
     syms = list(out)
     dem = subprocess.run(["c++filt"], input="\n".join(syms), capture_output=True, text=True, check=True).stdout.split("\n")
@@ -88,9 +93,15 @@ def family(name):
 
 
 def main():
+    renames = []
+    while len(sys.argv) > 3 and sys.argv[1] == "--rename":
+        renames.append(sys.argv[2:4])
+        del sys.argv[1:4]
     if len(sys.argv) != 3:
         sys.exit(__doc__)
-    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+    old, new = kernels(sys.argv[1], bool(renames)), kernels(sys.argv[2], bool(renames))
+    for pat, repl in renames:
+        old = {re.sub(pat, repl, n): v for n, v in old.items()}
     counts = collections.Counter(family(n) for n in new)
     bad, pcrel = [], []
     for n in sorted(set(old) - set(new)):

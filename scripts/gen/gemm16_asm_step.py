@@ -3,7 +3,7 @@
 instruction stream -- every read, DMA, wait and barrier at a fixed MFMA position, and NOTHING the
 compiler adds (hipcc's waitcnt pass inserted conservative lgkmcnt waits at the loop header and around
 the pinned regions of the HIP form).  Schedules:
-  SPLIT  kGemm4Split (gemm.hip): the buffer just read released per operand, waits + barriers after
+  SPLIT  kGemm4Split (gemm_16bit.hip): the buffer just read released per operand, waits + barriers after
          MFMAs 21, 51 (lgkmcnt(0)) and 92 (vmcnt(13)), the next step's reads spread over the rest;
   L0/L1  the same release structure with each barrier one MFMA after its wait, and the two event
          orders the library's MT256x256x64 kernel alternates between waves on even and odd SIMDs.

@@ -4,7 +4,7 @@
 #ifndef NO_STAMPS
 #define QZ_STAMPS_G16
 #endif
-#include "../../quantizations_amd/csrc/gemm.hip"
+#include "../../quantizations_amd/csrc/gemm_16bit.hip"
 namespace qz { int &gemm16_sched() { static int v = 971; return v; } }  // the library keeps it in gemv.hip
 
 #include <algorithm>
@@ -40,9 +40,9 @@ int main(int argc, char **argv) {
   const unsigned g = (unsigned)(((M + 255) / 256) * ((T + 255) / 256));
   struct V { std::string n; std::function<void()> f; std::vector<double> us; unsigned long long st[8 * 4 * 16]; };
   std::vector<V> vs;
-#define ADD(SK_, S_) vs.push_back({"SK=" #SK_ " S=" #S_, [=]() { hipLaunchKernelGGL((k_gemm16_4d<QZ_DT_F16, SK_, 16, 112, S_>), dim3(g), dim3(256), 0, 0, p); }, {}, {}})
+#define ADD(S_) vs.push_back({"4d S=" #S_, [=]() { hipLaunchKernelGGL((k_gemm16_4d<QZ_DT_F16, S_>), dim3(g), dim3(256), 0, 0, p); }, {}, {}})
 #define ADDQ(S_) vs.push_back({"4q S=" #S_, [=]() { hipLaunchKernelGGL((k_gemm16_4q<QZ_DT_F16, S_>), dim3(std::min(g, 256u)), dim3(256), 0, 0, p); }, {}, {}})
-  ADD(64, 0); ADD(65, 0); ADDQ(0); ADDQ(128); ADDQ(384); ADDQ(392);
+  ADD(0); ADDQ(0); ADDQ(128); ADDQ(384); ADDQ(392);
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   for (auto &v : vs) v.f();
   CK(hipDeviceSynchronize());
@@ -59,7 +59,7 @@ int main(int argc, char **argv) {
       CK(hipMemcpyFromSymbol(v.st, HIP_SYMBOL(g_qz_stamp_g16), sizeof(v.st)));
 #endif
     }
-  printf("M=%d K=%d T=%d fp16 (SK 65 = no DMAs: stale LDS, timing only)\n", M, K, T);
+  printf("M=%d K=%d T=%d fp16\n", M, K, T);
   printf("stamp columns (cycles, medians over 8 workgroups x 4 waves): prologue = start->after prologue barrier;"
          " step 20 from its start: wait1 before/after, wait2 before/after, wait3 before/after, next step start;"
          " loop end -> after vmcnt(0); epilogue\n");

@@ -2,8 +2,7 @@
 // tokens) with B fragments loaded straight from memory (TB = 0) vs staged
 // through a wave-private LDS image (TB = token bucket), NF4 + double quant,
 // 16 rotating weight copies, stream parked behind a spin kernel.
-#include "../../quantizations_amd/csrc/gemm.hip"
-namespace qz { int &gemm16_sched() { static int v = 0; return v; } }  // the library keeps it in gemv.hip
+#include "../../quantizations_amd/csrc/gemm_mt.hip"
 
 #include <cstdio>
 #include <cstdlib>

@@ -1,4 +1,4 @@
-"""CPU: the kernels of the adapter-bank route (k_gemv_4bit_mt_grouped_lora in gemm.hip,
+"""CPU: the kernels of the adapter-bank route (k_gemv_4bit_mt_grouped_lora in gemm_mt.hip,
 k_lora_shrink_mt in lora.hip), read from libquantizations.so's gfx950 code objects as
 tests/test_kernel_resources.py reads the decode GEMVs: no scratch, no spills, no AGPR use, and each
 multi-token kernel in the occupancy class of its plain twin k_gemv_4bit_mt_grouped<same arguments>

@@ -202,6 +202,22 @@ int qz_gemm_16bit_ok(int T, int M, int K, const void *X, int ldx, const void *W,
  * (0 = no split). */
 long long qz_gemm_4bit_workspace_size(int T, int M, int K);
 
+/* Input gradient of the fused 4-bit GEMM (extension; the backward of a frozen 4-bit linear layer,
+ * bitsandbytes' MatMul4Bit.backward): dX[T,K] = dY[T,M] . W[M,K].  W is decoded tile-by-tile into
+ * LDS as exactly the values qz_dequantize_4bit would store and read back transposed
+ * (ds_read_b64_tr_b16) as the MFMA operand; fp32 accumulation.  dY/dX share `dtype` (F16 or
+ * BF16); ldg/ldx are row strides in elements.  Requires K % 64 == 0, M % 8 == 0, ldg % 8 == 0,
+ * 16-B-aligned dY and B, blocksize >= 64 (else QZ_ERR_SHAPE / QZ_ERR_BLOCKSIZE: nothing is
+ * launched).  T == 0 or K == 0: nothing to do; M == 0: dX is zero-filled.  For small grids the
+ * weight rows are split across workgroups: pass a workspace of
+ * qz_gemm_4bit_dgrad_workspace_size(T, M, K) bytes (fp32 partials) to enable it; with less (or
+ * none) the split is reduced accordingly. */
+long long qz_gemm_4bit_dgrad_workspace_size(int T, int M, int K);
+int qz_gemm_4bit_dgrad(int T, int M, int K, const void *dY, int ldg, int dtype, const unsigned char *B,
+                       int quant_type, int blocksize, const float *absmax, const unsigned char *qabsmax,
+                       const float *absmax2, const float *code2, const float *offset, int blocksize2, void *dX,
+                       int ldx, void *workspace, long long workspace_bytes, void *stream);
+
 /* 4-bit blockwise quantisation (quantize_4bit, core.py:507-559): A[n] of
  * `a_dtype` -> packed out[(n+1)/2] + fp32 absmax[ceil(n/blocksize)]. */
 int qz_quantize_4bit(const void *A, int a_dtype, long long n, int blocksize, int quant_type, float *absmax,

@@ -12,12 +12,14 @@ from .core import (  # noqa: F401
     dequantize_4bit,
     dequantize_blockwise,
     gemm_4bit,
+    gemm_4bit_dgrad,
     gemv_4bit,
     get_4bit_type,
     get_ptr,
     quantize_4bit,
     quantize_blockwise,
 )
+from .autograd import MatMul4Bit  # noqa: F401
 from .modules import Linear4bit, matmul_4bit  # noqa: F401
 
 __version__ = "0.1.0"

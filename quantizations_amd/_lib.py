@@ -94,6 +94,8 @@ SIGNATURES = {
                             _p, _p, _p, _ll, _p, _f, _p],
     "qz_gemm_4bit": [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _ll, _p],
     "qz_gemm_4bit_workspace_size": [_i, _i, _i],
+    "qz_gemm_4bit_dgrad": [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _ll, _p],
+    "qz_gemm_4bit_dgrad_workspace_size": [_i, _i, _i],
     "qz_gemm_16bit": [_i, _i, _i, _p, _i, _i, _p, _p, _p, _i, _p],
     "qz_gemm_16bit_ok": [_i, _i, _i, _p, _i, _p, _p, _i],
     "qz_gemm_4bit_grouped": [_i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p],
@@ -128,7 +130,8 @@ SIGNATURES = {
     "qz_gemv_set_knob": [ctypes.c_char_p, _i],
     "qz_version": [],
 }
-RESTYPES = {"qz_absmax_mean_workspace": _ll, "qz_gemm_4bit_workspace_size": _ll, "qz_exchange_bytes": _ll,
+RESTYPES = {"qz_absmax_mean_workspace": _ll, "qz_gemm_4bit_workspace_size": _ll, "qz_gemm_4bit_dgrad_workspace_size": _ll,
+            "qz_exchange_bytes": _ll,
             "qz_greedy_step_work_bytes": _ll}
 
 

@@ -718,6 +718,68 @@ def gemm_4bit(A: Tensor, B: Tensor, state: QuantState, bias: Optional[Tensor] = 
     return torch.nn.functional.linear(A, W.to(A.dtype), None if bias is None else bias.to(A.dtype))
 
 
+# Backward (autograd.MatMul4Bit): the input gradient of a frozen 4-bit linear layer.
+_DGRAD_FUSED_MAX_T_ENV = os.environ.get("QZ_DGRAD_FUSED_MAX_T")
+DGRAD_FUSED_MAX_TOKENS = int(_DGRAD_FUSED_MAX_T_ENV) if _DGRAD_FUSED_MAX_T_ENV else None   # None = the table
+
+
+def dgrad_fused_max_tokens(M: int, K: int) -> int:
+    """Largest token count gemm_4bit_dgrad's auto route sends to the fused kernel for an M x K
+    weight.  An explicit QZ_DGRAD_FUSED_MAX_T (DGRAD_FUSED_MAX_TOKENS) replaces the table.  The
+    table is the measured crossover against dequantize_4bit + the library GEMM, whole routes
+    (scripts/dgrad_lowT_sweep.py, profiles/dgrad_lowT_sweep.txt; T in 1, 16, 64, ..., 2048): the
+    largest measured T up to which the fused route is never slower.  Many weight rows over few
+    columns (4096 x 4096, 14336 x 4096)
+    keep the fused kernel ahead through 512 tokens and behind at 1024; few rows (1024 x 4096)
+    or many columns (4096 x 14336) through 128, behind or level at 256."""
+    if DGRAD_FUSED_MAX_TOKENS is not None:
+        return DGRAD_FUSED_MAX_TOKENS
+    return 512 if M >= 4096 and K <= 4096 else 128
+
+
+def _dgrad_fused_ok(G2: Tensor, state: QuantState, M: int, K: int) -> bool:
+    return (G2.dtype in (torch.float16, torch.bfloat16) and K % 64 == 0 and M % 8 == 0
+            and state.blocksize >= 64 and G2.stride(0) % 8 == 0 and G2.data_ptr() % 16 == 0)
+
+
+def gemm_4bit_dgrad(G: Tensor, B: Tensor, state: QuantState, route: str = "auto") -> Tensor:
+    """Input gradient of x . W^T for a 4-bit W [M, K]: G[..., M] . W -> [..., K], in G's dtype
+    (bitsandbytes' MatMul4Bit.backward: grad_out @ dequantize_4bit(W)).
+
+    route "fused": the MFMA kernel qz_gemm_4bit_dgrad, which decodes W in LDS to exactly the values
+    dequantize_4bit(B, state, out_dtype=G.dtype) stores and reads the image transposed (fp16/bf16
+    G, K % 64 == 0, M % 8 == 0, blocksize >= 64; ValueError otherwise).  "dequant": full-weight
+    dequantize_4bit, then the library GEMM -- the bnb route; fp32 G always takes it.  "auto": fused
+    up to dgrad_fused_max_tokens(M, K) tokens, dequant above."""
+    if route not in ("auto", "fused", "dequant"):
+        raise ValueError(f"route must be 'auto', 'fused' or 'dequant', got {route!r}")
+    M, K = state.shape[0], state.shape[1]
+    if G.shape[-1] != M:
+        raise ValueError(f"G has {G.shape[-1]} features, the 4-bit weight has {M} rows")
+    lead = G.shape[:-1]
+    G2 = G.reshape(-1, M)
+    if G2.stride(-1) != 1 or G2.stride(0) % 8 != 0 or G2.data_ptr() % 16 != 0:
+        G2 = G2.contiguous()
+    T = G2.shape[0]
+    if T == 0 or K == 0 or M == 0:
+        return torch.zeros((*lead, K), dtype=G.dtype, device=G.device)
+    fused_ok = _dgrad_fused_ok(G2, state, M, K)
+    if route == "fused" and not fused_ok:
+        raise ValueError("gemm_4bit_dgrad: the fused kernel needs fp16/bf16 gradients, K % 64 == 0, M % 8 == 0 "
+                         "and blocksize >= 64")
+    if fused_ok and (route == "fused" or (route == "auto" and T <= dgrad_fused_max_tokens(M, K))):
+        out = torch.empty((T, K), dtype=G.dtype, device=G.device)
+        ws_bytes = int(lib.qz_gemm_4bit_dgrad_workspace_size(T, M, K))
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=G.device) if ws_bytes > 0 else None
+        check(lib.qz_gemm_4bit_dgrad(T, M, K, ptr(G2), G2.stride(0), dtype_code(G.dtype), ptr(B),
+                                     _lib.QUANT_TYPES[state.quant_type], state.blocksize, *state.scale_args(),
+                                     ptr(out), K, ptr(ws), ws_bytes, _lib.stream_of(G)), "gemm_4bit_dgrad")
+        return out.reshape(*lead, K)
+    cd = G.dtype if G.dtype in (torch.float16, torch.bfloat16) else None
+    W = dequantize_4bit(B, state, out_dtype=cd).t()          # [M, K], contiguous
+    return torch.matmul(G, W.to(G.dtype))
+
+
 # Token counts the multi-token kernel (and so the grouped batched-decode launch) takes
 MT_MIN_TOKENS, MT_MAX_TOKENS, MT_K_MULTIPLE = 2, 16, 256
 

@@ -27,8 +27,16 @@ from . import _lib
 _SUPPORTED = (torch.float16, torch.bfloat16, torch.float32)
 
 
+def _needs_grad(*xs: torch.Tensor) -> bool:
+    """Autograd is recording and one of the activations requires grad.  These launches write into
+    fresh buffers and have no backward, so every *_supported predicate declines such an input: a
+    model patched by integration.fuse_* then runs the original torch op instead of detaching."""
+    return torch.is_grad_enabled() and any(x.requires_grad for x in xs)
+
+
 def rms_norm_supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
-    return (x.is_cuda and x.dtype in _SUPPORTED and weight.dtype == x.dtype and weight.device == x.device
+    return (not _needs_grad(x)
+            and x.is_cuda and x.dtype in _SUPPORTED and weight.dtype == x.dtype and weight.device == x.device
             and weight.dim() == 1 and x.dim() >= 1 and x.shape[-1] == weight.shape[0] and weight.is_contiguous()
             and x.stride(-1) == 1)
 
@@ -49,7 +57,8 @@ def rms_norm(x: torch.Tensor, weight: torch.Tensor, eps: float) -> torch.Tensor:
 
 
 def add_rms_norm_supported(x: torch.Tensor, residual: torch.Tensor, weight: torch.Tensor) -> bool:
-    return (rms_norm_supported(x, weight) and residual.dtype == x.dtype and residual.device == x.device
+    return (not _needs_grad(residual) and rms_norm_supported(x, weight)
+            and residual.dtype == x.dtype and residual.device == x.device
             and residual.shape == x.shape and x.is_contiguous() and residual.is_contiguous())
 
 
@@ -74,6 +83,8 @@ def _strides3(t: torch.Tensor):
 
 def rope_supported(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
                    unsqueeze_dim: int = 1) -> bool:
+    if _needs_grad(q, k):
+        return False
     if unsqueeze_dim != 1 or q.dim() != 4 or k.dim() != 4 or cos.dim() != 3 or sin.shape != cos.shape:
         return False
     if not (q.is_cuda and q.dtype in _SUPPORTED and k.dtype == q.dtype and cos.dtype == q.dtype
@@ -110,7 +121,8 @@ def rope_qk(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor, sin: torch.Tens
 
 
 def silu_mul_supported(g: torch.Tensor, u: torch.Tensor) -> bool:
-    return (g.is_cuda and g.dtype in _SUPPORTED and u.dtype == g.dtype and u.device == g.device
+    return (not _needs_grad(g, u)
+            and g.is_cuda and g.dtype in _SUPPORTED and u.dtype == g.dtype and u.device == g.device
             and g.shape == u.shape and g.is_contiguous() and u.is_contiguous())
 
 
@@ -133,7 +145,8 @@ def decode_attention_supported(q: torch.Tensor, cos: torch.Tensor, key_cache: to
     [B, 1, *]), 16-bit activations, a contiguous static cache [B, Hkv, L, D] with D in {64, 128}
     and Hq/Hkv <= 8, a bool mask [B or 1, 1, 1, L], cos/sin [B or 1, 1, D] and an int64 position
     on the GPU.  Metadata only: nothing is launched or allocated."""
-    if not (q.is_cuda and q.dtype in (torch.float16, torch.bfloat16) and q.dim() == 3 and q.shape[1] == 1):
+    if _needs_grad(q) or not (q.is_cuda and q.dtype in (torch.float16, torch.bfloat16) and q.dim() == 3
+                              and q.shape[1] == 1):
         return False
     if key_cache.dim() != 4 or value_cache.shape != key_cache.shape:
         return False
@@ -249,8 +262,9 @@ DENSE_K = (4096, 8192)   # the widths qz_gemv_dense takes (Llama-3 8B / 70B)
 
 def gemv_dense_supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
     """One token through an unquantised fp16/bf16 [M, K] weight (the lm_head) with qz_gemv_dense."""
-    if not (x.is_cuda and weight.is_cuda and x.device == weight.device and x.dtype == weight.dtype
-            and x.dtype in (torch.float16, torch.bfloat16) and weight.dim() == 2 and weight.is_contiguous()):
+    if _needs_grad(x) or not (x.is_cuda and weight.is_cuda and x.device == weight.device and x.dtype == weight.dtype
+                              and x.dtype in (torch.float16, torch.bfloat16) and weight.dim() == 2
+                              and weight.is_contiguous()):
         return False
     K = weight.shape[1]
     return (K in DENSE_K and x.shape[-1] == K and x.numel() == K and x.is_contiguous()

@@ -1,10 +1,19 @@
 """``Linear4bit`` -- drop-in for ``bnb.nn.Linear4bit`` / the reference
-``modules.Linear4bit`` (reference modules.py:67-151), inference only.
+``modules.Linear4bit`` (reference modules.py:67-151).
 
 Dispatch (reference modules.py:28-64): a single-token input
 (``A.numel() == A.shape[-1]``) runs the fused decode GEMV; anything else runs
 the fused prefill GEMM (MFMA).  Both consume the 4-bit weight directly -- no
 dequantised copy of W is ever materialised in HBM on the supported shapes.
+
+Training through the frozen weight (QLoRA): when autograd is recording and the
+input requires grad, the layer runs on its own through ``autograd.MatMul4Bit``
+-- the same forward launches, so the same output bits, plus a backward that
+returns the input gradient (core.gemm_4bit_dgrad) and the bias gradient.  The
+decode fast paths (groups, the gate/up pair, the residual epilogue, the fused
+adapter launches) step aside for such an input; adapters and banks are added
+with torch ops that autograd differentiates.  The 4-bit weight itself never gets
+a gradient.  Every other call keeps its path, launch count and output bits.
 """
 from __future__ import annotations
 
@@ -14,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, lora
+from .autograd import MatMul4Bit
 from .core import (MT_MAX_TOKENS, Params4bit, QuantState, dequantize_4bit, exact_codes_for, gemm_4bit,
                    gemm_4bit_grouped, gemv_4bit, gemv_4bit_grouped, gemv_4bit_pair_silu, grouped_tokens_ok)
 
@@ -24,9 +34,17 @@ def matmul_4bit(A: torch.Tensor, B: torch.Tensor, quant_state: QuantState, out: 
     weight (the reference passes ``weight.t()``; only its storage is used).
     `exact_codes` (decode only): see gemv_4bit; Linear4bit sets it from compute_dtype."""
     assert quant_state is not None
+    if grad_route(A):
+        return MatMul4Bit.apply(A, B, out, bias, quant_state, exact_codes)
     if A.numel() == A.shape[-1]:
         return gemv_4bit(A, B, out, state=quant_state, bias=bias, exact_codes=exact_codes)
     return gemm_4bit(A, B, quant_state, bias=bias)
+
+
+def grad_route(*xs: torch.Tensor) -> bool:
+    """Autograd is recording and one of xs requires grad: the call must stay differentiable, so it
+    goes through MatMul4Bit and torch ops instead of the launches that write into fresh buffers."""
+    return torch.is_grad_enabled() and any(x.requires_grad for x in xs)
 
 
 def _as_dtype(out: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
@@ -57,7 +75,9 @@ class DecodeGroup:
 
     @staticmethod
     def accepts(x: torch.Tensor) -> bool:
-        """Decode-shaped input: 1..MT_MAX_TOKENS tokens."""
+        """Decode-shaped input: 1..MT_MAX_TOKENS tokens (and not one autograd has to follow)."""
+        if grad_route(x):
+            return False
         k = x.shape[-1]
         return k > 0 and 1 <= x.numel() // k <= MT_MAX_TOKENS
 
@@ -139,7 +159,7 @@ def linear4bit_silu_pair(group: DecodeGroup, x: torch.Tensor):
     single token, in one launch (core.gemv_4bit_pair_silu; an RMSNorm absorbed by fuse_prenorm
     is applied inside too).  None when that launch does not take the case: the caller then calls
     the members (the grouped launch) and multiplies."""
-    if group._compute is not _linear4bit_group_compute or len(group.members) != 2:
+    if group._compute is not _linear4bit_group_compute or len(group.members) != 2 or grad_route(x):
         return None
     if not (x.is_cuda and x.numel() == x.shape[-1] and x.dtype in (torch.float16, torch.bfloat16)):
         return None
@@ -261,11 +281,20 @@ class Linear4bit(nn.Linear):
         xin = self._input(x)
         bias = None if self.bias is None else self.bias.to(xin.dtype)
         ad = self.adapter
+        bank = self.adapter_bank
+        if grad_route(x):
+            # the layer on its own: MatMul4Bit for the base term, the composed torch terms on top
+            out = matmul_4bit(xin, self.weight, bias=bias, quant_state=qs,
+                              exact_codes=exact_codes_for(self.compute_dtype))
+            if ad is not None:
+                out = out + lora.composed_term(ad, xin, out.dtype)
+            if bank is not None:
+                out = out + lora.composed_bank_term(bank, xin, out.dtype)
+            return _as_dtype(out, inp_dtype)
         if ad is not None and lora.fused_ok(ad, xin):   # one token: shrink, then the GEMV carries B . t
             t, _ = lora.shrink(xin, [ad])
             return _as_dtype(gemv_4bit(xin, self.weight, state=qs, bias=bias, lora=(ad.B, t),
                                        exact_codes=exact_codes_for(self.compute_dtype)), inp_dtype)
-        bank = self.adapter_bank
         if bank is not None:
             _, tps = lora.bank_rows(bank, xin)
             items = [(self.weight, qs, bias)]
@@ -287,7 +316,8 @@ class Linear4bit(nn.Linear):
         with the add in the decode GEMV's epilogue (one launch, bit-identical to the torch
         add) when x is a single token this layer decodes on its own; otherwise the two ops."""
         qs = self.weight.quant_state
-        if (qs is not None and x.is_cuda and x.numel() == x.shape[-1] and self.__dict__.get("_qz_group") is None
+        if (not grad_route(x, residual)
+                and qs is not None and x.is_cuda and x.numel() == x.shape[-1] and self.__dict__.get("_qz_group") is None
                 and self.adapter_bank is None
                 and residual.dtype == x.dtype and residual.device == x.device and residual.is_contiguous()
                 and residual.numel() == qs.shape[0] and residual.shape[:-1] == x.shape[:-1]):

@@ -129,6 +129,7 @@ class RowShardedLinear4bit(nn.Module):
     def local_forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._local_matmul is not None:
             return self._local_matmul(x, self)
+        _inference_only(x, "RowShardedLinear4bit")
         from .core import gemm_4bit, gemv_4bit
         if x.numel() == x.shape[-1]:
             return gemv_4bit(x, self.packed, state=self.state, bias=self.bias, block_base=self.block_base,
@@ -162,12 +163,21 @@ class RowShardedLinear4bit(nn.Module):
                 and residual.dtype == x.dtype and residual.device == x.device and residual.is_contiguous()
                 and residual.numel() == self.out_features and residual.shape[:-1] == x.shape[:-1]
                 and self.__dict__.get("_qz_group") is None):
+            _inference_only(x, "RowShardedLinear4bit.forward_residual", residual)
             from .core import gemv_4bit
             rows = residual.reshape(-1)[self.r0:self.r1]
             y = gemv_4bit(x, self.packed, state=self.state, bias=self.bias, block_base=self.block_base,
                           exact_codes=self.exact_codes, residual=rows)
             return self.gather_rows(y).reshape(residual.shape)
         return residual + self(x_in)
+
+
+def _inference_only(x: torch.Tensor, what: str, *more: torch.Tensor) -> None:
+    """The multi-GPU layouts are inference-only: their kernel launches write into fresh buffers, so
+    an input autograd has to follow would be detached silently.  Raise instead."""
+    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in more)):
+        raise NotImplementedError(f"{what}: the tensor-parallel layouts are inference-only (the input requires "
+                                  "grad); run under torch.no_grad() or train on the unsharded Linear4bit")
 
 
 def _group_input(group, x: torch.Tensor, fused_ok: bool):
@@ -275,6 +285,7 @@ def sharded_silu_pair(group, x: torch.Tensor) -> Optional[torch.Tensor]:
     if g._local_matmul is not None:  # test hook (CPU): the two local products and torch's SiLU
         h = torch.nn.functional.silu(g._local_matmul(xin, g)) * u._local_matmul(xin, u)
     else:
+        _inference_only(x, "sharded_silu_pair")
         from .core import gemv_4bit_pair_silu
         h = gemv_4bit_pair_silu(xin, [(g.packed, g.state, g.bias, g.block_base), (u.packed, u.state, u.bias, u.block_base)],
                                 exact_codes=g.exact_codes, norm=norm)
@@ -358,6 +369,7 @@ class RowParallelLinear4bit(nn.Module):
         if self._local_matmul is not None:
             y = self._local_matmul(x_local, self)
         else:
+            _inference_only(x_local, "the row-parallel Linear4bit shard")
             from .core import gemm_4bit, gemv_4bit
             if x_local.numel() == x_local.shape[-1]:
                 y = gemv_4bit(x_local, self.packed, state=self.state, bias=self.bias, exact_codes=self.exact_codes)

@@ -30,6 +30,8 @@ SHAPES = [
     (130, 4096, 256, 64),   # long contraction on a 2-column-tile grid: split-M engages; T across 128
     (300, 264, 4096, 64),   # many column tiles, short contraction, no split
     (16, 200, 256, 128),    # blocksize above 64
+    (16, 4104, 256, 64),    # 65 steps over 13 splits of 5: a ragged last split (4 1/8 steps) and a partial last step
+    (130, 4104, 256, 64),   # the same split under the 128-token tile, T across it
 ]
 _ID = [f"T{t}-M{m}-K{k}-bs{b}" for t, m, k, b in SHAPES]
 
@@ -111,6 +113,28 @@ def test_dgrad_dequant_route(random_cases, i, dtype):
     dX3 = gemm_4bit_dgrad(G.reshape(1, *G.shape), packed, st)
     assert dX3.shape == (1, G.shape[0], st.shape[1])
     assert_close(dX3.float().cpu().numpy(), ref, dtype, f"auto {_ID[i]}")
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("T,M,K", [(130, 4096, 256), (16, 200, 192)], ids=["split", "unsplit"])
+def test_dgrad_strided_gradient(T, M, K, dtype):
+    """G as a column slice of a wider tensor (row stride M + 64 > M, what autograd hands the layer when
+    the output was sliced): the kernel reads it in place through ldg, bit-identical to the copy's result."""
+    from quantizations_amd import _lib
+    from quantizations_amd.core import gemm_4bit_dgrad
+
+    packed, st, Wd = _weight(M, K, "nf4", True, 64, dtype, seed=T + M)
+    wide = torch.randn(T, M + 64, generator=torch.Generator().manual_seed(T)).to(dtype).to(DEV)
+    G = wide[:, 32:32 + M]
+    assert G.stride(0) == M + 64 and not G.is_contiguous() and G.data_ptr() % 16 == 0
+    assert (_lib.lib.qz_gemm_4bit_dgrad_workspace_size(T, M, K) > 0) == (M == 4096)
+    dX = gemm_4bit_dgrad(G, packed, st, route="fused")
+    assert torch.equal(dX, gemm_4bit_dgrad(G.contiguous(), packed, st, route="fused"))
+    assert_close(dX.float().cpu().numpy(), (G.double() @ Wd.double()).cpu().numpy(), dtype, f"strided T={T} M={M}")
+    # the C-ABI reads the view itself: a stride below M is refused, nothing launched
+    out = torch.empty(T, K, dtype=dtype, device=DEV)
+    assert _lib.lib.qz_gemm_4bit_dgrad(T, M, K, G.data_ptr(), M - 8, _lib.dtype_code(dtype), packed.data_ptr(), _lib.NF4,
+                                       64, *st.scale_args(), out.data_ptr(), K, 0, 0, 0) == _lib.QZ_ERR_SHAPE
 
 
 def test_dgrad_routes_that_do_not_apply():

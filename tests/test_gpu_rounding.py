@@ -8,6 +8,9 @@ DEV = torch.device("cuda")
 
 
 def test_dequant_store_tie_cases(orc, oracle_vectors):
+    """The one halfway case that exposed the scalar fp16 convert.  The `ties` family
+    (tests/weight_families.py, test_gpu_weight_range.test_dequantize_families_bit_exact) generalises
+    it: >= 32 fp16 and >= 8 bf16 halfway cases per code and parity, and subnormal-range ones."""
     from quantizations_amd import _lib
     from quantizations_amd.core import dequantize_4bit, quantize_4bit
 

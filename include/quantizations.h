@@ -359,6 +359,29 @@ int qz_decode_attention(int dtype, int B, int Hq, int Hkv, int D, int L, const v
 long long qz_greedy_step_work_bytes(int B, long long V);
 int qz_greedy_step(const void *logits, int dtype, int B, long long V, long long row, long long *hist,
                    long long hist_row, long long hist_len, long long *pos, long long *tok, void *work, void *stream);
+/* qz_sample_step: the sampled pick and its feedback, qz_greedy_step's twin (five short
+ *   launches, csrc/sample.hip; every parameter is read on the device, so a captured graph follows
+ *   new values).  For b < B, with p = *pos, u = uniform[b*uniform_row + min(max(p, 0), hist_len-1)]
+ *   in [0, 1) and everything in fp32:
+ *   - temperature[b] <= 0, or a row maximum that is not finite (NaN, +inf, all -inf): the pick
+ *     is qz_greedy_step's;
+ *   - else s_i = logits[b*row + i] / temperature[b]; -inf entries are never kept; top-k
+ *     (1 <= top_k[b] < V, any other value: off) keeps s_i >= the k-th largest score, ties at the
+ *     threshold included; top-p (P = top_p[b], P >= 1: off) keeps i iff the softmax mass (over the
+ *     top-k survivors) of the scores strictly above s_i is < P, so tie groups stay or go whole and
+ *     the maximal group always stays; with w_i = exp(s_i - max s) over the kept set and R = sum w,
+ *     the token is the smallest kept i whose inclusive prefix of w in index order is > u * R (the
+ *     last kept index if rounding leaves none).
+ *   Then hist[b*hist_row + p] = token (skipped when p is outside [0, hist_len)), tok[b] = token, and
+ *   *pos = p + 1.  F16/BF16 logits (QZ_ERR_DTYPE otherwise), unit element stride, row >= V;
+ *   temperature/top_p fp32 [B], top_k int32 [B], uniform fp32 [B, hist_len]; int64 hist/pos/tok;
+ *   work: qz_sample_step_work_bytes(B, V) bytes, 16-B aligned, any content.  Temperatures must
+ *   leave distinct logits distinct finite fp32 scores.  B <= 65535 (else QZ_ERR_SHAPE). */
+long long qz_sample_step_work_bytes(int B, long long V);
+int qz_sample_step(const void *logits, int dtype, int B, long long V, long long row, const float *temperature,
+                   const int *top_k, const float *top_p, const float *uniform, long long uniform_row,
+                   long long *hist, long long hist_row, long long hist_len, long long *pos, long long *tok,
+                   void *work, void *stream);
 /* qz_gemv_dense: the model's fp16/bf16 lm_head for one decode token (transformers keeps it
  *   unquantised): y[m] = sum_k W[m*K + k] x[k] for m < M, fp32 accumulation, rounded once to
  *   dtype; K in {4096, 8192}, W and x 16-B aligned (else QZ_ERR_SHAPE, nothing launched). */

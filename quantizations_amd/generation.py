@@ -1,0 +1,236 @@
+"""Decoding a model whose linears are Linear4bit at the speed of the benchmark's loop: the fused
+single-GPU layout (prepare_for_decode), a decode step captured once into a HIP graph together with
+its token pick and feedback (DecodeSession), and generate() on top of both.
+
+The pick is layer_ops.sample_step -- per-stream temperature, top-k and top-p read on the device, so
+a replay follows set_sampling() -- or layer_ops.greedy_step when every stream is greedy at capture.
+Equal-length prompts on one GPU only; no penalties, no beams.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence, Union
+
+import torch
+
+from . import layer_ops as _ops
+
+STOP_CHECK_EVERY = 16   # generate(): steps between host looks at the history
+
+
+def prepare_for_decode(model, *, fuse: bool = True, layer_ops: bool = True, prenorm: bool = True, glue: bool = True,
+                       lm_head: bool = True) -> dict:
+    """The single-GPU decode layout of a model after replace_with_bnb_linear, in the benchmark's
+    order: one grouped GEMV per q/k/v and gate/up set, the one-launch layer ops (norms, rotary,
+    attention, residual adds, the MLP pair), the RMSNorms absorbed into the grouped launches, the
+    step's mask and rotary tables, and the dense lm_head GEMV.  Returns the number of patches of
+    each kind.  A second call patches nothing and returns the first call's counts."""
+    done = model.__dict__.get("_qz_prepared")
+    if done is not None:
+        return dict(done)
+    from . import integration as I
+
+    counts = {"groups": 0, "layer_ops": 0, "prenorm": 0, "glue": 0, "lm_head": 0}
+    if fuse:
+        counts["groups"] = I.fuse_projection_groups(model)
+    if layer_ops:
+        counts["layer_ops"] = I.fuse_layer_ops(model)
+        if prenorm and fuse:
+            counts["prenorm"] = I.fuse_prenorm(model)
+        if glue:
+            counts["glue"] = I.fuse_decode_glue(model)
+        if lm_head:
+            counts["lm_head"] = I.fuse_lm_head(model)
+    model.__dict__["_qz_prepared"] = dict(counts)
+    return counts
+
+
+def _per_stream(value, batch: int, dtype, device, name: str) -> torch.Tensor:
+    t = torch.as_tensor(value, dtype=dtype).reshape(-1)
+    if t.numel() == 1:
+        t = t.expand(batch)
+    if t.numel() != batch:
+        raise ValueError(f"{name}: one value or one per stream ({batch}), got {t.numel()}")
+    return t.to(device)
+
+
+class DecodeSession:
+    """One batch of decode streams over `model`: the StaticCache and the static buffers a captured
+    step reads and writes -- tok [B, 1], pos [1], hist [B, max_len] (int64), uniform [B, max_len],
+    temperature / top_p [B] (float32), top_k [B] (int32).  hist holds the sequence itself (prompt,
+    then the picked tokens); pos is the position of `tok`, the newest token, which the next step feeds:
+    that step writes its pick to hist[:, pos + 1], drawing it with uniform[:, pos], and advances
+    pos.  prefill() runs the prompt and picks the first new token."""
+
+    def __init__(self, model, batch: int, max_len: int, *, graph: bool = True):
+        from transformers.cache_utils import StaticCache
+
+        if batch < 1 or max_len < 1:
+            raise ValueError("DecodeSession: batch and max_len must be positive")
+        self.model, self.batch, self.max_len = model, int(batch), int(max_len)
+        self.device = next(model.parameters()).device
+        self.graph = bool(graph) and self.device.type == "cuda"
+        dev = self.device
+        # two slots of slack: the capture's warm-up runs write the cache at pos and pos + 1
+        self.cache = StaticCache(config=model.config, max_cache_len=self.max_len + 2)
+        self.tok = torch.zeros((batch, 1), dtype=torch.int64, device=dev)
+        self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
+        # the pick kernels write hist[b, *pos] and read uniform[b, *pos] (the bench's convention: the
+        # column of the token that was fed), so they get the history shifted by one element: column
+        # p of `_hist_next` is column p + 1 of the sequence.  Two columns of slack, like the cache.
+        width = max_len + 2
+        store = torch.zeros(batch * width + 1, dtype=torch.int64, device=dev)
+        self._hist_full = store[:batch * width].view(batch, width)
+        self._hist_next = store[1:].view(batch, width)
+        self.hist = self._hist_full[:, :max_len]
+        self._uniform_full = torch.zeros((batch, width), dtype=torch.float32, device=dev)
+        self.uniform = self._uniform_full[:, :max_len]
+        self.temperature = torch.zeros(batch, dtype=torch.float32, device=dev)   # greedy until set_sampling
+        self.top_k = torch.zeros(batch, dtype=torch.int32, device=dev)
+        self.top_p = torch.ones(batch, dtype=torch.float32, device=dev)
+        self._pos_ids = self.pos.view(1, 1).expand(batch, 1)
+        self._graph = None
+        self._greedy_only = True   # host knowledge: no stream has a temperature > 0
+        self._prefilled = False
+        self._next = 0   # tokens in hist (host copy of pos + 1)
+
+    def set_sampling(self, temperature=None, top_k=None, top_p=None) -> None:
+        """Scalars or one value per stream, written in place: the next step, replayed or not, uses
+        them.  temperature <= 0 makes a stream greedy.  A graph captured while every stream was greedy
+        holds greedy_step alone, so a stream cannot start sampling after that capture."""
+        if temperature is not None:
+            t = _per_stream(temperature, self.batch, torch.float32, self.device, "temperature")
+            sampled = bool((t > 0).any())
+            if self._graph is not None and self._greedy_only and sampled:
+                raise ValueError("set_sampling: this session captured a greedy-only step")
+            self.temperature.copy_(t)
+            if self._graph is None:
+                self._greedy_only = not sampled
+        if top_k is not None:
+            self.top_k.copy_(_per_stream(top_k, self.batch, torch.int32, self.device, "top_k"))
+        if top_p is not None:
+            self.top_p.copy_(_per_stream(top_p, self.batch, torch.float32, self.device, "top_p"))
+
+    def seed(self, generator: Union[torch.Generator, int, None]) -> None:
+        """Refill `uniform` (one number in [0, 1) per stream and position) with torch.rand; the token
+        at sequence index i is drawn with uniform[:, i - 1]."""
+        if isinstance(generator, int):
+            generator = torch.Generator(device=self.device).manual_seed(generator)
+        if generator is None:
+            self.uniform.copy_(torch.rand(self.uniform.shape, device=self.device))
+        else:
+            self.uniform.copy_(torch.rand(self.uniform.shape, generator=generator, device=generator.device))
+
+    def _pick(self, logits: torch.Tensor) -> None:
+        if self._greedy_only and logits.is_cuda:
+            _ops.greedy_step(logits, self._hist_next, self.pos, self.tok)
+        else:
+            _ops.sample_step(logits, self._hist_next, self.pos, self.tok, self.temperature, self.top_k, self.top_p,
+                             self._uniform_full)
+
+    @torch.inference_mode()
+    def prefill(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> None:
+        """Run the prompts ([B, S], equal lengths) and pick each stream's first new token."""
+        if attention_mask is not None and not bool(attention_mask.bool().all()):
+            raise ValueError("DecodeSession.prefill: padded prompts are not supported (attention_mask holds a zero)")
+        if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
+            raise ValueError(f"DecodeSession.prefill: input_ids must be [{self.batch}, S]")
+        S = input_ids.shape[1]
+        if S < 1 or S >= self.max_len:
+            raise ValueError("DecodeSession.prefill: the prompt must be shorter than max_len")
+        if self._prefilled:
+            raise ValueError("DecodeSession.prefill: a session takes one prompt; open another for the next")
+        ids = input_ids.to(self.device)
+        self.hist[:, :S] = ids
+        self.pos.fill_(S - 1)                          # the last prompt token; the pick makes it S
+        out = self.model(input_ids=ids, past_key_values=self.cache,
+                         cache_position=torch.arange(S, device=self.device), use_cache=True)
+        self._pick(out.logits[:, -1])
+        self._prefilled = True
+        self._next = S + 1
+
+    def _step(self) -> None:
+        lo = self.model(input_ids=self.tok, past_key_values=self.cache, cache_position=self.pos,
+                        position_ids=self._pos_ids, use_cache=True).logits
+        self._pick(lo[:, -1])
+
+    def _cache_lengths(self):
+        """Each StaticLayer's device-side length (the decode attention advances it in-kernel)."""
+        out = [getattr(layer, "cumulative_length", None) for layer in getattr(self.cache, "layers", [])]
+        if not out or not all(isinstance(t, torch.Tensor) for t in out):
+            raise RuntimeError("DecodeSession: this transformers StaticCache keeps no per-layer device-side "
+                               "cumulative_length to restore after the capture's warm-up runs")
+        return out
+
+    def _capture(self) -> None:
+        # two warm-up runs on a side stream, as the benchmark does; they advance the cache lengths,
+        # pos, tok and hist, which are put back so that no position is consumed (the keys and values
+        # they wrote lie past the restored length: masked now, overwritten by the steps that follow)
+        state = [self.tok, self.pos, self._hist_full] + self._cache_lengths()
+        saved = [t.clone() for t in state]
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                self._step()
+        torch.cuda.current_stream().wait_stream(s)
+        for t, v in zip(state, saved):
+            t.copy_(v)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._step()
+        for t, v in zip(state, saved):
+            t.copy_(v)
+        self._graph = g
+
+    @torch.inference_mode()
+    def step(self) -> None:
+        """One token per stream: the forward of `tok` at position `pos`, the pick,
+        hist[:, pos + 1] = tok = token, pos += 1.  With graph=True the first call captures the step and every call replays it."""
+        if not self._prefilled:
+            raise ValueError("DecodeSession.step: prefill first")
+        if self._next >= self.max_len:
+            raise ValueError("DecodeSession.step: the history is full (max_len tokens)")
+        self._next += 1
+        if not self.graph:
+            self._step()
+            return
+        if self._graph is None:
+            self._capture()
+        self._graph.replay()
+
+
+@torch.inference_mode()
+def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: bool = False,
+             temperature: Union[float, Sequence[float]] = 1.0, top_k: Union[int, Sequence[int]] = 0,
+             top_p: Union[float, Sequence[float]] = 1.0, generator=None, eos_token_id: Optional[int] = None,
+             attention_mask: Optional[torch.Tensor] = None, graph: bool = True) -> torch.Tensor:
+    """input_ids [B, S] (equal-length prompts) followed by up to max_new_tokens picked tokens per
+    stream: greedy, or with do_sample temperature / top_k / top_p (scalars or one per stream; a
+    temperature <= 0 keeps that stream greedy) drawn from `generator` (a torch.Generator or a seed).
+    With eos_token_id the history is looked at on the host every 16 steps: a stream's tokens after
+    its first EOS are that EOS, and the call returns once every stream has stopped.  Returns int64
+    [B, S + new] on the model's device."""
+    if input_ids.dim() != 2:
+        raise ValueError("generate: input_ids must be [B, S]")
+    B, S = input_ids.shape
+    if max_new_tokens < 1:
+        return input_ids.clone()
+    sess = DecodeSession(model, B, S + max_new_tokens, graph=graph)
+    if do_sample:
+        sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
+        sess.seed(generator)
+    sess.prefill(input_ids, attention_mask)        # writes hist[:, S]
+    n = 1
+    while n < max_new_tokens:
+        sess.step()
+        n += 1
+        if eos_token_id is not None and (n % STOP_CHECK_EVERY == 0):
+            new = sess.hist[:, S:S + n].cpu()       # one copy
+            if bool((new == eos_token_id).any(1).all()):
+                break
+    out = sess.hist[:, :S + n].clone()
+    if eos_token_id is not None:
+        new = out[:, S:]
+        ended = (new == eos_token_id).cumsum(1) > 0
+        new[ended] = eos_token_id
+    return out

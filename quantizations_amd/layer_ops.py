@@ -10,6 +10,9 @@ projections (csrc/layer_ops.hip, C-ABI include/quantizations.h):
 * ``add_rms_norm`` -- LlamaDecoderLayer's ``residual + h`` followed by the
   post-attention RMSNorm (modeling_llama.py:317-321).
 
+``greedy_step`` / ``sample_step`` are a decode loop's token pick with its feedback (csrc/sample.hip for the
+sampled one, which alone has a composed torch route: fp32 or CPU logits).
+
 None of them is in the reference (it leaves them to transformers).  They exist
 because at batch-1 decode the eager torch forms cost ~8, ~10 and 2 dependent
 launches per call, which dominate the step once the Linear4bit GEMVs are
@@ -281,3 +284,102 @@ def gemv_dense(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     _lib.check(_lib.lib.qz_gemv_dense(M, K, x.data_ptr(), _lib.dtype_code(x.dtype), weight.data_ptr(), y.data_ptr(),
                                       _lib.stream_of(x)), "qz_gemv_dense")
     return y
+
+
+def sample_step_supported(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, tok: torch.Tensor,
+                          temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+                          uniform: torch.Tensor) -> bool:
+    """What qz_sample_step takes: fp16 / bf16 logits [B, V] on the GPU with unit element stride, and
+    the buffers sample_step documents, contiguous on the same device.  Metadata only: nothing is
+    launched or allocated."""
+    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype in (torch.float16, torch.bfloat16)
+            and logits.dim() == 2 and logits.stride(-1) == 1 and logits.stride(0) >= logits.shape[1]):
+        return False
+    B = logits.shape[0]
+    if B > 65535:
+        return False
+    for t, dt in ((hist, torch.int64), (pos, torch.int64), (tok, torch.int64), (temperature, torch.float32),
+                  (top_k, torch.int32), (top_p, torch.float32), (uniform, torch.float32)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.device == logits.device and t.is_contiguous()):
+            return False
+    return (hist.dim() == 2 and hist.shape[0] == B and uniform.shape == hist.shape and pos.numel() == 1
+            and tok.numel() == B and temperature.shape == top_k.shape == top_p.shape == (B,))
+
+
+def _sample_step_composed(logits, hist, pos, tok, temperature, top_k, top_p, uniform) -> None:
+    """qz_sample_step's semantics in torch ops (sort-based, fp32, no host read: capturable)."""
+    B, V = logits.shape
+    H = hist.shape[1]
+    z = logits.float()
+    ninf = torch.full((), float("-inf"), device=z.device)
+    zmax = z.max(dim=1).values                                             # NaN if the row holds one
+    greedy = ~(temperature > 0) | ~torch.isfinite(zmax)
+    T = torch.where(temperature > 0, temperature, torch.ones_like(temperature))
+    s = torch.where(torch.isneginf(z), ninf, z / T[:, None])
+    vals, _ = s.sort(dim=1, descending=True)
+    kon = (top_k >= 1) & (top_k < V)
+    kth = vals.gather(1, (top_k.long().clamp(1, V) - 1)[:, None])
+    s = torch.where(~kon[:, None] | (s >= kth), s, ninf)
+    vals = torch.where(~kon[:, None] | (vals >= kth), vals, ninf)
+    smax = vals[:, :1]
+    ws = torch.exp(vals - smax)
+    cum = ws.cumsum(1)
+    Z = cum[:, -1:]
+    first = torch.ones_like(vals, dtype=torch.bool)
+    first[:, 1:] = vals[:, 1:] != vals[:, :-1]
+    above = torch.where(first, cum - ws, torch.zeros_like(cum)).cummax(1).values   # mass strictly above
+    keep_sorted = (vals > ninf) & ((top_p >= 1)[:, None] | (above < top_p[:, None] * Z) | (vals == smax))
+    cut = torch.where(keep_sorted, vals, torch.full_like(vals, float("inf"))).min(dim=1, keepdim=True).values
+    w = torch.where((s >= cut) & (s > ninf), torch.exp(s - smax), torch.zeros_like(s))
+    cdf = w.cumsum(1)
+    p = pos.reshape(1)
+    col = p.clamp(0, max(H - 1, 0))              # a [1] index tensor: index_select / index_copy_ read it on the device
+    u = uniform.index_select(1, col)[:, 0] if H else torch.zeros(B, device=z.device)
+    hit = cdf > (u * cdf[:, -1])[:, None]
+    last = (V - 1) - (w.flip(1) > 0).int().argmax(1)
+    pick = torch.where(hit.any(1), hit.int().argmax(1), last)
+    token = torch.where(greedy, logits.argmax(-1), pick)
+    if H:
+        inside = (p >= 0) & (p < H)
+        hist.index_copy_(1, col, torch.where(inside, token, hist.index_select(1, col)[:, 0])[:, None])
+    tok.copy_(token.view(tok.shape))
+    pos.add_(1)
+
+
+def sample_step(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, tok: torch.Tensor,
+                temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, uniform: torch.Tensor,
+                *, composed: bool = False) -> None:
+    """A decode loop's sampled pick and feedback (qz_sample_step; include/quantizations.h states the
+    rules): per stream b, temperature[b] <= 0 or a non-finite row maximum picks greedy_step's token;
+    else scores logits / temperature, top_k[b] (ties at the threshold kept; outside [1, V): off),
+    top_p[b] (tie groups whole, >= 1: off) and the inverse CDF in index order at
+    uniform[b, min(pos, H - 1)].  Then hist[b, pos] = token, tok[b] = token, pos += 1.  logits [B, V]
+    (unit element stride), temperature / top_p float32 [B], top_k int32 [B], uniform float32 [B, H],
+    hist [B, H] / pos [1] / tok [B] contiguous int64, all on one device.  Every value is read on the
+    device, so a captured call follows in-place changes.  fp32 or CPU logits (sample_step_supported
+    is false), or composed=True, take the same rules in torch ops."""
+    if logits.dim() != 2 or logits.stride(-1) != 1:
+        raise ValueError("sample_step: logits must be [B, V] with unit element stride")
+    B, V = logits.shape
+    for t in (hist, pos, tok):
+        if t.dtype != torch.int64 or t.device != logits.device or not t.is_contiguous():
+            raise ValueError("sample_step: hist/pos/tok must be contiguous int64 on the logits' device")
+    if hist.dim() != 2 or hist.shape[0] != B or pos.numel() != 1 or tok.numel() != B:
+        raise ValueError("sample_step: hist [B, H], pos [1], tok [B]")
+    for t, dt, name in ((temperature, torch.float32, "temperature"), (top_k, torch.int32, "top_k"),
+                        (top_p, torch.float32, "top_p")):
+        if t.dtype != dt or t.device != logits.device or t.shape != (B,) or not t.is_contiguous():
+            raise ValueError(f"sample_step: {name} must be contiguous {dt} [B] on the logits' device")
+    if (uniform.dtype != torch.float32 or uniform.device != logits.device or uniform.shape != hist.shape
+            or not uniform.is_contiguous()):
+        raise ValueError("sample_step: uniform must be contiguous float32 [B, H] on the logits' device")
+    if composed or not sample_step_supported(logits, hist, pos, tok, temperature, top_k, top_p, uniform):
+        if V:
+            _sample_step_composed(logits, hist, pos, tok, temperature, top_k, top_p, uniform)
+        return
+    work = torch.empty(_lib.lib.qz_sample_step_work_bytes(B, V), dtype=torch.uint8, device=logits.device)
+    _lib.check(_lib.lib.qz_sample_step(logits.data_ptr(), _lib.dtype_code(logits.dtype), B, V, logits.stride(0),
+                                       temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
+                                       uniform.data_ptr(), uniform.shape[1], hist.data_ptr(), hist.shape[1],
+                                       hist.shape[1], pos.data_ptr(), tok.data_ptr(), work.data_ptr(),
+                                       _lib.stream_of(logits)), "qz_sample_step")

@@ -339,6 +339,21 @@ int qz_decode_attention(int dtype, int B, int Hq, int Hkv, int D, int L, const v
                         const void *sin, long long cs_row, void *k_cache, void *v_cache, const void *mask,
                         long long mask_b, long long mask_j, long long *pos, unsigned int *arrive, void *out,
                         long long out_row, float *work, float scale, void *stream);
+/* qz_decode_attention with a position per stream and no mask operand: pos is int64 [B] (device,
+ * read only).  p_b = pos[b] is the cache slot that receives stream b's new k/v and its last visible
+ * key: key j of stream b is visible iff 0 <= j <= p_b.  No arrival word and no in-kernel advance:
+ * every layer of a step reads the same pos, and the pick (qz_*_step_streams) advances it.
+ *   - out[b] and the cache rows written are bit-identical to qz_decode_attention on stream b alone
+ *     (B = 1 views, mask[j] = (j <= p_b), *pos = p_b); cache rows above p_b may hold anything, NaN
+ *     included, and are never loaded where their whole 128-key chunk lies above p_b;
+ *   - p_b < 0 or p_b >= L: out[b] is NaN, stream b's cache is not written, other streams are
+ *     unaffected.
+ * Every other operand, `work` and the status codes are qz_decode_attention's. */
+int qz_decode_attention_streams(int dtype, int B, int Hq, int Hkv, int D, int L, const void *q, long long q_row,
+                                const void *k, long long k_row, const void *v, long long v_row, const void *cos,
+                                const void *sin, long long cs_row, void *k_cache, void *v_cache,
+                                const long long *pos, void *out, long long out_row, float *work, float scale,
+                                void *stream);
 
 /* Decode-step glue of the host model (transformers' LlamaModel.forward), one launch each in place
  * of the small torch kernels it issues per step.  Not part of the Linear4bit path; the
@@ -382,6 +397,22 @@ int qz_sample_step(const void *logits, int dtype, int B, long long V, long long 
                    const int *top_k, const float *top_p, const float *uniform, long long uniform_row,
                    long long *hist, long long hist_row, long long hist_len, long long *pos, long long *tok,
                    void *work, void *stream);
+/* qz_greedy_step_streams / qz_sample_step_streams: the same picks (the same kernels, the same work
+ *   sizes) with the feedback per stream: pos int64 [B], live int32 [B], stop int64 [B] (a token id,
+ *   -1: none), limit int64 [B].  For a stream with live[b] != 0 and p = pos[b]: the token is what
+ *   the twin above picks for that logits row alone at *pos = p (u = uniform[b, clamp(p)]); then
+ *   hist[b*hist_row + p] = token (p inside [0, hist_len)), tok[b] = token, pos[b] = p + 1, and
+ *   last live[b] = 0 if token == stop[b] or p + 1 >= limit[b].  A stream with live[b] == 0 has
+ *   nothing written: tok, pos, hist and live keep their values.  Argument errors as the twins'. */
+int qz_greedy_step_streams(const void *logits, int dtype, int B, long long V, long long row, long long *hist,
+                           long long hist_row, long long hist_len, long long *pos, int *live,
+                           const long long *stop, const long long *limit, long long *tok, void *work,
+                           void *stream);
+int qz_sample_step_streams(const void *logits, int dtype, int B, long long V, long long row,
+                           const float *temperature, const int *top_k, const float *top_p, const float *uniform,
+                           long long uniform_row, long long *hist, long long hist_row, long long hist_len,
+                           long long *pos, int *live, const long long *stop, const long long *limit,
+                           long long *tok, void *work, void *stream);
 /* qz_gemv_dense: the model's fp16/bf16 lm_head for one decode token (transformers keeps it
  *   unquantised): y[m] = sum_k W[m*K + k] x[k] for m < M, fp32 accumulation, rounded once to
  *   dtype; K in {4096, 8192}, W and x 16-B aligned (else QZ_ERR_SHAPE, nothing launched). */

@@ -21,6 +21,12 @@ from .core import (  # noqa: F401
 )
 from .autograd import MatMul4Bit  # noqa: F401
 from .modules import Linear4bit, matmul_4bit  # noqa: F401
-from .generation import DecodeSession, generate, prepare_for_decode  # noqa: F401
+from .generation import (  # noqa: F401
+    DecodeSession,
+    StreamSession,
+    generate,
+    generate_ragged,
+    prepare_for_decode,
+)
 
 __version__ = "0.1.0"

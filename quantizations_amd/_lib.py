@@ -92,6 +92,10 @@ SIGNATURES = {
     "qz_gemm_4bit_grouped_lora": [_i, _p, _p, _p, _i, _p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p],
     "qz_decode_attention": [_i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p, _ll, _ll,
                             _p, _p, _p, _ll, _p, _f, _p],
+    "qz_decode_attention_streams": [_i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p, _p,
+                                    _ll, _p, _f, _p],
+    "qz_greedy_step_streams": [_p, _i, _i, _ll, _ll, _p, _ll, _ll, _p, _p, _p, _p, _p, _p, _p],
+    "qz_sample_step_streams": [_p, _i, _i, _ll, _ll, _p, _p, _p, _p, _ll, _p, _ll, _ll, _p, _p, _p, _p, _p, _p, _p],
     "qz_gemm_4bit": [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _ll, _p],
     "qz_gemm_4bit_workspace_size": [_i, _i, _i],
     "qz_gemm_4bit_dgrad": [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _ll, _p],

@@ -39,10 +39,11 @@ struct DecodeAttnArgs {
   const void *cos, *sin;     // [B or 1, D], row b at b * cs (cs = 0: one row for all)
   long long cs;
   void *kc, *vc;             // caches [B, Hkv, L, D], contiguous
-  const unsigned char *mask;  // bool, element (b, j) at b * mb + j * mj
+  const unsigned char *mask;  // bool, element (b, j) at b * mb + j * mj (STREAMS: none, key j visible iff j <= pos[b])
   long long mb, mj;
-  long long *pos;            // write position p (StaticLayer.cumulative_length), advanced by one
-  unsigned int *arrive;      // arrival counter, zero between launches
+  long long *pos;            // write position p (StaticLayer.cumulative_length), advanced by one;
+                             // STREAMS: [B] positions, read only
+  unsigned int *arrive;      // arrival counter, zero between launches (STREAMS: unused)
   void *out;                 // [B, Hq * D], row b at b * os
   long long os;
   float *part;               // nsplit > 1: [B, Hkv, nsplit, G, D + 2]
@@ -114,7 +115,10 @@ template <int D> struct AttnLds {
 
 // One query head `hq` of sequence `b` over key chunk `split`, by the 256 threads of the calling
 // workgroup (q, k and v come from a previous launch: plain loads).  Returns the position p it read (the caller advances *a.pos once every head is done).
-template <int DT, int D>
+// STREAMS (qz_decode_attention_streams): p is a.pos[b], the stream's own position, and the mask is
+// j <= p computed here; everything after those two reads is the same code, so a stream's row
+// carries the bits of a B = 1 launch with that mask and position.
+template <int DT, int D, bool STREAMS = false>
 __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, int split, int hq, int b,
                                                       const AttnLds<D> &S) {
   constexpr int ES = DT == QZ_DT_F32 ? 4 : 2;
@@ -142,7 +146,7 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
   //    position j -- whatever the mask says (a masked row is dropped after it arrives) -- for
   //    caches up to kAttnSpecL positions; a longer cache is read after its mask, so a long
   //    static cache early in a sequence does not stream its masked rows.
-  const long long p = *a.pos;
+  const long long p = STREAMS ? a.pos[b] : *a.pos;
   const bool rt = t < H2;
   float x1 = 0.f, x2 = 0.f, c1 = 0.f, c2 = 0.f, s1 = 0.f, s2 = 0.f, k1 = 0.f, k2 = 0.f;
   uint32_t vnew = 0u;
@@ -158,7 +162,9 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
     c1 = load_f32<DT>(cb, t); c2 = load_f32<DT>(cb, t + H2);
     s1 = load_f32<DT>(sb, t); s2 = load_f32<DT>(sb, t + H2);
   }
-  const unsigned char mk = in_l ? a.mask[(long long)b * a.mb + j * a.mj] : (unsigned char)0;
+  unsigned char mk;
+  if constexpr (STREAMS) mk = (in_l && j <= p) ? (unsigned char)1 : (unsigned char)0;
+  else mk = in_l ? a.mask[(long long)b * a.mb + j * a.mj] : (unsigned char)0;
   u32x4 kr[NW / 4], vr[NW / 4];
   const bool spec = L <= kAttnSpecL;
   const u32x4 *kp = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(a.kc) + ((crow + j) * D + half * H2) * ES);

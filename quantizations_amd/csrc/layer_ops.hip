@@ -243,6 +243,39 @@ __global__ __launch_bounds__(256) void k_decode_attn(DecodeAttnArgs a) {
   }
 }
 
+// The same head with a position per stream (qz_decode_attention_streams): p_b = pos[b] is the slot of
+// the new k/v and the last visible key; no mask operand, no arrival counter, pos is not advanced (the
+// pick does that).  A chunk that starts above p_b leaves before any cache load -- a short stream in a
+// long static cache costs its own chunks only -- and with nsplit > 1 leaves the neutral partial the
+// masked chunk of k_decode_attn leaves (zero sums, m = -inf, l = 0), so the combine is unchanged.  A
+// position outside [0, L) writes no cache row and makes the stream's output NaN (0 / 0 in the
+// combine; stored directly with one chunk).
+template <int DT, int D>
+__global__ __launch_bounds__(256) void k_decode_attn_streams(DecodeAttnArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_v[kAttnChunk * (D / 2)];
+  __shared__ __attribute__((aligned(16))) unsigned char s_small[AttnLds<D>::kSmallBytes];
+  const int split = blockIdx.x, hq = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
+  const long long p = a.pos[b];
+  const bool bad = p < 0 || p >= a.L;
+  if (bad || (long long)split * kAttnChunk > p) {   // uniform over the workgroup
+    if (t < D) {
+      const float fill = bad ? __builtin_nanf("") : 0.0f;
+      if (a.nsplit == 1) {
+        char *ob = reinterpret_cast<char *>(a.out) + ((long long)b * a.os + (long long)hq * D) * 2;
+        store_f32<DT>(ob, t, fill);   // one chunk starts at 0 <= p: only a bad position comes here
+      } else {
+        const int h = hq / a.G, gq = hq - h * a.G;
+        float *pp = a.part + ((((long long)b * a.Hkv + h) * a.nsplit + split) * a.G + gq) * (D + 2);
+        pp[t] = fill;
+        if (t == 0) { pp[D] = -INFINITY; pp[D + 1] = 0.0f; }
+      }
+    }
+    return;
+  }
+  const AttnLds<D> S{s_v, s_small};
+  decode_attn_head<DT, D, true>(a, split, hq, b, S);
+}
+
 // nsplit > 1: merge the chunk partials of one (b, kv head) -- out = sum_s e^(m_s - M) o_s /
 // sum_s e^(m_s - M) l_s with M = max_s m_s; empty chunks (m_s = -inf) weigh nothing
 template <int DT, int D>
@@ -270,6 +303,11 @@ __global__ __launch_bounds__(256) void k_decode_attn_combine(DecodeAttnArgs a) {
 template <int DT, int D>
 void launch_decode_attn(const DecodeAttnArgs &a, int B, hipStream_t s) {
   hipLaunchKernelGGL((k_decode_attn<DT, D>), dim3(a.nsplit, a.Hkv * a.G, B), dim3(256), 0, s, a);
+  if (a.nsplit > 1) hipLaunchKernelGGL((k_decode_attn_combine<DT, D>), dim3(a.Hkv, B), dim3(256), 0, s, a);
+}
+template <int DT, int D>
+void launch_decode_attn_streams(const DecodeAttnArgs &a, int B, hipStream_t s) {
+  hipLaunchKernelGGL((k_decode_attn_streams<DT, D>), dim3(a.nsplit, a.Hkv * a.G, B), dim3(256), 0, s, a);
   if (a.nsplit > 1) hipLaunchKernelGGL((k_decode_attn_combine<DT, D>), dim3(a.Hkv, B), dim3(256), 0, s, a);
 }
 
@@ -435,13 +473,18 @@ __global__ __launch_bounds__(256) void k_greedy_partial(const void *logits, long
     pi[(size_t)b * nb + blockIdx.x] = bi;
   }
 }
+// `live` null: one position word for the batch (qz_greedy_step).  Else (qz_greedy_step_streams) pos,
+// live, stop and limit hold a word per stream: a live stream writes hist[b, pos[b]], tok[b] and
+// pos[b] += 1, then clears live[b] on its stop token or at its limit; a stream that is not live
+// writes nothing.
 __global__ __launch_bounds__(256) void k_greedy_final(int B, long long V, int nb, const float *pv,
                                                       const long long *pi, long long *hist, long long hist_row,
-                                                      long long hist_len, long long *pos, long long *tok) {
+                                                      long long hist_len, long long *pos, long long *tok, int *live,
+                                                      const long long *stop, const long long *limit) {
   __shared__ float s_v[4];
   __shared__ long long s_i[4];
   const int tid = threadIdx.x;
-  const long long p = *pos;
+  const long long p0 = live ? 0 : *pos;
   for (int b = 0; b < B; ++b) {
     float best = -__builtin_inff();
     long long bi = V;
@@ -451,14 +494,19 @@ __global__ __launch_bounds__(256) void k_greedy_final(int B, long long V, int nb
       if (i != V && (bi == V || greedy_better(v, i, best, bi))) { best = v; bi = i; }
     }
     greedy_reduce_wg(best, bi, V, s_v, s_i);
-    if (tid == 0) {
+    if (tid == 0 && (!live || live[b] != 0)) {
+      const long long p = live ? pos[b] : p0;
       // a position past the history (a graph replayed more often than hist has columns) writes
       // nothing there: the token and the position still advance
       if (p >= 0 && p < hist_len) hist[(size_t)b * hist_row + p] = bi;
       tok[b] = bi;
+      if (live) {
+        pos[b] = p + 1;
+        if (bi == stop[b] || p + 1 >= limit[b]) live[b] = 0;
+      }
     }
   }
-  if (tid == 0) *pos = p + 1;
+  if (tid == 0 && !live) *pos = p0 + 1;
 }
 
 // ---- the host model's fp16 / bf16 lm_head for one decode token (not 4-bit: transformers keeps it
@@ -583,37 +631,66 @@ extern "C" int qz_silu_mul(const void *gate, const void *up, int dtype, long lon
   return (int)hipGetLastError();
 }
 
-extern "C" int qz_decode_attention(int dtype, int B, int Hq, int Hkv, int D, int L, const void *q, long long q_row,
-                                   const void *k, long long k_row, const void *v, long long v_row, const void *cos,
-                                   const void *sin, long long cs_row, void *k_cache, void *v_cache,
-                                   const void *mask, long long mask_b, long long mask_j, long long *pos,
-                                   unsigned int *arrive, void *out, long long out_row, float *work, float scale,
-                                   void *stream) {
+// The operand checks and the argument block the two decode attention entry points share (`others_ok`:
+// the shared-position form's mask and arrival word are there; it adds them to the block itself).  1: launch, 0: nothing to
+// do, negative: the status to return.
+static int decode_attn_args(int dtype, int B, int Hq, int Hkv, int D, int L, const void *q, long long q_row,
+                            const void *k, long long k_row, const void *v, long long v_row, const void *cos,
+                            const void *sin, long long cs_row, void *k_cache, void *v_cache, bool others_ok,
+                            const long long *pos, void *out, long long out_row, float *work, float scale,
+                            DecodeAttnArgs &a) {
   if (B < 0 || Hq < 0 || Hkv < 0 || D < 0 || L < 0) return QZ_ERR_ARG;
   if (B == 0 || Hq == 0) return 0;
   if (Hkv == 0 || Hq % Hkv != 0 || Hq / Hkv > kAttnMaxG || (D != 64 && D != 128) || L == 0) return QZ_ERR_SHAPE;
   if (B > 65535 || Hq > 65535) return QZ_ERR_SHAPE;
-  if (!q || !k || !v || !cos || !sin || !k_cache || !v_cache || !mask || !pos || !arrive || !out) return QZ_ERR_ARG;
+  if (!q || !k || !v || !cos || !sin || !k_cache || !v_cache || !others_ok || !pos || !out) return QZ_ERR_ARG;
   if (q_row < (long long)Hq * D || k_row < (long long)Hkv * D || v_row < (long long)Hkv * D || cs_row < 0 ||
       out_row < (long long)Hq * D)
     return QZ_ERR_ARG;
   // 16-B row loads of the caches; 4-B words of v
   if (((uintptr_t)k_cache | (uintptr_t)v_cache) % 16 != 0 || ((uintptr_t)v % 4) != 0 || (v_row % 2) != 0)
     return QZ_ERR_ARG;
-  DecodeAttnArgs a{};
   a.q = q; a.k = k; a.v = v; a.qs = q_row; a.ks = k_row; a.vs = v_row;
   a.cos = cos; a.sin = sin; a.cs = cs_row;
   a.kc = k_cache; a.vc = v_cache;
-  a.mask = reinterpret_cast<const unsigned char *>(mask); a.mb = mask_b; a.mj = mask_j;
-  a.pos = pos; a.arrive = arrive; a.out = out; a.os = out_row; a.part = work;
+  a.pos = const_cast<long long *>(pos);   // the streams kernel only reads it
+  a.out = out; a.os = out_row; a.part = work;
   a.Hkv = Hkv; a.G = Hq / Hkv; a.L = L; a.nsplit = (L + kAttnChunk - 1) / kAttnChunk; a.scale = scale;
   if (a.nsplit > 1 && !work) return QZ_ERR_ARG;
+  if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) return QZ_ERR_DTYPE;
+  return 1;
+}
+
+extern "C" int qz_decode_attention(int dtype, int B, int Hq, int Hkv, int D, int L, const void *q, long long q_row,
+                                   const void *k, long long k_row, const void *v, long long v_row, const void *cos,
+                                   const void *sin, long long cs_row, void *k_cache, void *v_cache,
+                                   const void *mask, long long mask_b, long long mask_j, long long *pos,
+                                   unsigned int *arrive, void *out, long long out_row, float *work, float scale,
+                                   void *stream) {
+  DecodeAttnArgs a{};
+  const int rc = decode_attn_args(dtype, B, Hq, Hkv, D, L, q, q_row, k, k_row, v, v_row, cos, sin, cs_row, k_cache,
+                                  v_cache, mask && arrive, pos, out, out_row, work, scale, a);
+  if (rc <= 0) return rc;
+  a.mask = reinterpret_cast<const unsigned char *>(mask); a.mb = mask_b; a.mj = mask_j;
+  a.arrive = arrive;
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case QZ_DT_F16: D == 64 ? launch_decode_attn<QZ_DT_F16, 64>(a, B, s) : launch_decode_attn<QZ_DT_F16, 128>(a, B, s); break;
-    case QZ_DT_BF16: D == 64 ? launch_decode_attn<QZ_DT_BF16, 64>(a, B, s) : launch_decode_attn<QZ_DT_BF16, 128>(a, B, s); break;
-    default: return QZ_ERR_DTYPE;
-  }
+  if (dtype == QZ_DT_F16) D == 64 ? launch_decode_attn<QZ_DT_F16, 64>(a, B, s) : launch_decode_attn<QZ_DT_F16, 128>(a, B, s);
+  else D == 64 ? launch_decode_attn<QZ_DT_BF16, 64>(a, B, s) : launch_decode_attn<QZ_DT_BF16, 128>(a, B, s);
+  return (int)hipGetLastError();
+}
+
+extern "C" int qz_decode_attention_streams(int dtype, int B, int Hq, int Hkv, int D, int L, const void *q,
+                                           long long q_row, const void *k, long long k_row, const void *v,
+                                           long long v_row, const void *cos, const void *sin, long long cs_row,
+                                           void *k_cache, void *v_cache, const long long *pos, void *out,
+                                           long long out_row, float *work, float scale, void *stream) {
+  DecodeAttnArgs a{};
+  const int rc = decode_attn_args(dtype, B, Hq, Hkv, D, L, q, q_row, k, k_row, v, v_row, cos, sin, cs_row, k_cache,
+                                  v_cache, true, pos, out, out_row, work, scale, a);
+  if (rc <= 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == QZ_DT_F16) D == 64 ? launch_decode_attn_streams<QZ_DT_F16, 64>(a, B, s) : launch_decode_attn_streams<QZ_DT_F16, 128>(a, B, s);
+  else D == 64 ? launch_decode_attn_streams<QZ_DT_BF16, 64>(a, B, s) : launch_decode_attn_streams<QZ_DT_BF16, 128>(a, B, s);
   return (int)hipGetLastError();
 }
 
@@ -657,15 +734,12 @@ extern "C" long long qz_greedy_step_work_bytes(int B, long long V) {
   return (long long)B * ((V + kGreedyChunk - 1) / kGreedyChunk) * 16;
 }
 
-extern "C" int qz_greedy_step(const void *logits, int dtype, int B, long long V, long long row, long long *hist,
-                              long long hist_row, long long hist_len, long long *pos, long long *tok, void *work,
-                              void *stream) {
-  if (B < 0 || V < 0 || row < 0 || hist_row < 0 || hist_len < 0) return QZ_ERR_ARG;
-  if (B == 0) return 0;
-  if (V == 0 || !logits || !hist || !pos || !tok || !work || row < V || (B > 1 && hist_row < hist_len))
-    return QZ_ERR_ARG;
+static int greedy_step_launch(const void *logits, int dtype, int B, long long V, long long row, long long *hist,
+                              long long hist_row, long long hist_len, long long *pos, long long *tok, int *live,
+                              const long long *stop, const long long *limit, void *work, void *stream) {
   const long long nbl = (V + kGreedyChunk - 1) / kGreedyChunk;
   if (nbl > 0x7FFFFFFFLL || B > 65535) return QZ_ERR_SHAPE;
+  if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16 && dtype != QZ_DT_F32) return QZ_ERR_DTYPE;
   const int nb = (int)nbl;
   float *pv = reinterpret_cast<float *>(work);
   long long *pi = reinterpret_cast<long long *>(reinterpret_cast<unsigned char *>(work) + (size_t)B * nb * 8);
@@ -676,11 +750,35 @@ extern "C" int qz_greedy_step(const void *logits, int dtype, int B, long long V,
   switch (dtype) {
     case QZ_DT_F16: hipLaunchKernelGGL((k_greedy_partial<QZ_DT_F16>), g, dim3(256), 0, s, logits, row, V, nb, pv, pi, vec); break;
     case QZ_DT_BF16: hipLaunchKernelGGL((k_greedy_partial<QZ_DT_BF16>), g, dim3(256), 0, s, logits, row, V, nb, pv, pi, vec); break;
-    case QZ_DT_F32: hipLaunchKernelGGL((k_greedy_partial<QZ_DT_F32>), g, dim3(256), 0, s, logits, row, V, nb, pv, pi, vec); break;
-    default: return QZ_ERR_DTYPE;
+    default: hipLaunchKernelGGL((k_greedy_partial<QZ_DT_F32>), g, dim3(256), 0, s, logits, row, V, nb, pv, pi, vec); break;
   }
-  hipLaunchKernelGGL(k_greedy_final, dim3(1), dim3(256), 0, s, B, V, nb, pv, pi, hist, hist_row, hist_len, pos, tok);
+  hipLaunchKernelGGL(k_greedy_final, dim3(1), dim3(256), 0, s, B, V, nb, pv, pi, hist, hist_row, hist_len, pos, tok,
+                     live, stop, limit);
   return (int)hipGetLastError();
+}
+
+extern "C" int qz_greedy_step(const void *logits, int dtype, int B, long long V, long long row, long long *hist,
+                              long long hist_row, long long hist_len, long long *pos, long long *tok, void *work,
+                              void *stream) {
+  if (B < 0 || V < 0 || row < 0 || hist_row < 0 || hist_len < 0) return QZ_ERR_ARG;
+  if (B == 0) return 0;
+  if (V == 0 || !logits || !hist || !pos || !tok || !work || row < V || (B > 1 && hist_row < hist_len))
+    return QZ_ERR_ARG;
+  return greedy_step_launch(logits, dtype, B, V, row, hist, hist_row, hist_len, pos, tok, nullptr, nullptr, nullptr,
+                            work, stream);
+}
+
+extern "C" int qz_greedy_step_streams(const void *logits, int dtype, int B, long long V, long long row,
+                                      long long *hist, long long hist_row, long long hist_len, long long *pos,
+                                      int *live, const long long *stop, const long long *limit, long long *tok,
+                                      void *work, void *stream) {
+  if (B < 0 || V < 0 || row < 0 || hist_row < 0 || hist_len < 0) return QZ_ERR_ARG;
+  if (B == 0) return 0;
+  if (V == 0 || !logits || !hist || !pos || !live || !stop || !limit || !tok || !work || row < V ||
+      (B > 1 && hist_row < hist_len))
+    return QZ_ERR_ARG;
+  return greedy_step_launch(logits, dtype, B, V, row, hist, hist_row, hist_len, pos, tok, live, stop, limit, work,
+                            stream);
 }
 
 extern "C" int qz_gemv_dense(int M, int K, const void *x, int dtype, const void *W, void *y, void *stream) {

@@ -21,6 +21,10 @@
 // One CU reads ~25 GB/s, so the two passes over all V logits spread over V/2048 workgroups per stream;
 // the scan reads 256 KiB of bins per stream with coalesced 16-B loads from 16 waves.  *pos is read
 // only by k_sample_scan and written only by k_sample_final, so the streams' workgroups never race.
+//
+// qz_sample_step_streams launches the same five kernels with a position per stream (pos_stride 1)
+// and the live / stop / limit words: a stream that is not live is still scanned (its row costs what
+// it cost before) but k_sample_final writes nothing of it.
 #include <limits.h>
 
 #include "common.h"
@@ -203,8 +207,8 @@ template <int DT>
 __global__ __launch_bounds__(kScanThreads) void k_sample_scan(long long V, int nb, const float *temperature,
                                                               const int *top_k, const float *top_p,
                                                               const float *uniform, long long uniform_row,
-                                                              long long hist_len, const long long *pos, void *work,
-                                                              long long sbytes) {
+                                                              long long hist_len, const long long *pos,
+                                                              long long pos_stride, void *work, long long sbytes) {
   __shared__ float s_v[16];
   __shared__ long long s_i[16];
   __shared__ unsigned s_c[256];
@@ -227,7 +231,7 @@ __global__ __launch_bounds__(kScanThreads) void k_sample_scan(long long V, int n
   }
   greedy_reduce<16>(best, bi, V, s_v, s_i);
   if (tid == 0) {
-    const long long p = *pos;
+    const long long p = pos[(size_t)b * pos_stride];
     float u = 0.0f;
     if (hist_len > 0) {
       const long long q = p < 0 ? 0 : (p < hist_len ? p : hist_len - 1);
@@ -400,8 +404,9 @@ __global__ __launch_bounds__(256) void k_sample_chunk(const void *logits, long l
 template <int DT>
 __global__ __launch_bounds__(256) void k_sample_final(const void *logits, long long row, long long V, int nb,
                                                       long long *hist, long long hist_row, long long hist_len,
-                                                      long long *pos, long long *tok, void *work, long long sbytes,
-                                                      bool vec) {
+                                                      long long *pos, int *live, const long long *stop,
+                                                      const long long *limit, long long *tok, void *work,
+                                                      long long sbytes, bool vec) {
   __shared__ float s4[4];
   __shared__ int s_chunk, s_lastc, s_loc;
   __shared__ float s_base;
@@ -472,11 +477,16 @@ __global__ __launch_bounds__(256) void k_sample_final(const void *logits, long l
       if (fin >= 0) token = (long long)chunk * kSampleChunk + fin;
     }
   }
-  if (tid == 0) {
+  if (tid == 0 && (!live || live[b] != 0)) {
     // a position past the history writes nothing there: the token and the position still advance
     if (p >= 0 && p < hist_len) hist[(size_t)b * hist_row + p] = token;
     tok[b] = token;
-    if (b == 0) *pos = p + 1;
+    if (live) {   // a word per stream: advance it, then retire the stream on its stop token or at its limit
+      pos[b] = p + 1;
+      if (token == stop[b] || p + 1 >= limit[b]) live[b] = 0;
+    } else if (b == 0) {
+      *pos = p + 1;
+    }
   }
 }
 
@@ -490,15 +500,11 @@ extern "C" long long qz_sample_step_work_bytes(int B, long long V) {
   return (long long)B * stream_bytes((V + kSampleChunk - 1) / kSampleChunk);
 }
 
-extern "C" int qz_sample_step(const void *logits, int dtype, int B, long long V, long long row,
+static int sample_step_launch(const void *logits, int dtype, int B, long long V, long long row,
                               const float *temperature, const int *top_k, const float *top_p, const float *uniform,
                               long long uniform_row, long long *hist, long long hist_row, long long hist_len,
-                              long long *pos, long long *tok, void *work, void *stream) {
-  if (B < 0 || V < 0 || row < 0 || uniform_row < 0 || hist_row < 0 || hist_len < 0) return QZ_ERR_ARG;
-  if (B == 0 || V == 0) return QZ_OK;
-  if (!logits || !temperature || !top_k || !top_p || !uniform || !hist || !pos || !tok || !work || row < V ||
-      (uintptr_t)work % 16 != 0 || (B > 1 && (hist_row < hist_len || uniform_row < hist_len)))
-    return QZ_ERR_ARG;
+                              long long *pos, long long pos_stride, int *live, const long long *stop,
+                              const long long *limit, long long *tok, void *work, void *stream) {
   if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) return QZ_ERR_DTYPE;
   const long long nbl = (V + kSampleChunk - 1) / kSampleChunk;
   if (nbl > 0x7FFFFFFFLL || B > 65535) return QZ_ERR_SHAPE;
@@ -511,12 +517,41 @@ extern "C" int qz_sample_step(const void *logits, int dtype, int B, long long V,
 #define QZ_SAMPLE_LAUNCH(DT)                                                                                        \
   hipLaunchKernelGGL((k_sample_hist<DT>), g, dim3(256), 0, s, logits, row, V, nb, temperature, work, sbytes, vec);  \
   hipLaunchKernelGGL((k_sample_scan<DT>), dim3((unsigned)B), dim3(kScanThreads), 0, s, V, nb, temperature, top_k,   \
-                     top_p, uniform, uniform_row, hist_len, pos, work, sbytes);                                     \
+                     top_p, uniform, uniform_row, hist_len, pos, pos_stride, work, sbytes);                         \
   hipLaunchKernelGGL((k_sample_chunk<DT>), g, dim3(256), 0, s, logits, row, V, nb, work, sbytes, vec);              \
   hipLaunchKernelGGL((k_sample_final<DT>), dim3((unsigned)B), dim3(256), 0, s, logits, row, V, nb, hist, hist_row,  \
-                     hist_len, pos, tok, work, sbytes, vec)
+                     hist_len, pos, live, stop, limit, tok, work, sbytes, vec)
   if (dtype == QZ_DT_F16) { QZ_SAMPLE_LAUNCH(QZ_DT_F16); }
   else { QZ_SAMPLE_LAUNCH(QZ_DT_BF16); }
 #undef QZ_SAMPLE_LAUNCH
   return (int)hipGetLastError();
+}
+
+extern "C" int qz_sample_step(const void *logits, int dtype, int B, long long V, long long row,
+                              const float *temperature, const int *top_k, const float *top_p, const float *uniform,
+                              long long uniform_row, long long *hist, long long hist_row, long long hist_len,
+                              long long *pos, long long *tok, void *work, void *stream) {
+  if (B < 0 || V < 0 || row < 0 || uniform_row < 0 || hist_row < 0 || hist_len < 0) return QZ_ERR_ARG;
+  if (B == 0 || V == 0) return QZ_OK;
+  if (!logits || !temperature || !top_k || !top_p || !uniform || !hist || !pos || !tok || !work || row < V ||
+      (uintptr_t)work % 16 != 0 || (B > 1 && (hist_row < hist_len || uniform_row < hist_len)))
+    return QZ_ERR_ARG;
+  return sample_step_launch(logits, dtype, B, V, row, temperature, top_k, top_p, uniform, uniform_row, hist, hist_row,
+                            hist_len, pos, 0, nullptr, nullptr, nullptr, tok, work, stream);
+}
+
+extern "C" int qz_sample_step_streams(const void *logits, int dtype, int B, long long V, long long row,
+                                      const float *temperature, const int *top_k, const float *top_p,
+                                      const float *uniform, long long uniform_row, long long *hist,
+                                      long long hist_row, long long hist_len, long long *pos, int *live,
+                                      const long long *stop, const long long *limit, long long *tok, void *work,
+                                      void *stream) {
+  if (B < 0 || V < 0 || row < 0 || uniform_row < 0 || hist_row < 0 || hist_len < 0) return QZ_ERR_ARG;
+  if (B == 0 || V == 0) return QZ_OK;
+  if (!logits || !temperature || !top_k || !top_p || !uniform || !hist || !pos || !live || !stop || !limit || !tok ||
+      !work || row < V || (uintptr_t)work % 16 != 0 ||
+      (B > 1 && (hist_row < hist_len || uniform_row < hist_len)))
+    return QZ_ERR_ARG;
+  return sample_step_launch(logits, dtype, B, V, row, temperature, top_k, top_p, uniform, uniform_row, hist, hist_row,
+                            hist_len, pos, 1, live, stop, limit, tok, work, stream);
 }

@@ -4,7 +4,10 @@ its token pick and feedback (DecodeSession), and generate() on top of both.
 
 The pick is layer_ops.sample_step -- per-stream temperature, top-k and top-p read on the device, so
 a replay follows set_sampling() -- or layer_ops.greedy_step when every stream is greedy at capture.
-Equal-length prompts on one GPU only; no penalties, no beams.
+DecodeSession / generate() take equal-length prompts and move every stream together; StreamSession
+/ generate_ragged() keep a position per stream on the device (prompts of different lengths, a
+finished stream's row handed to the next prompt without recapturing).  One GPU only; no penalties,
+no beams.
 """
 from __future__ import annotations
 
@@ -234,3 +237,242 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
         ended = (new == eos_token_id).cumsum(1) > 0
         new[ended] = eos_token_id
     return out
+
+
+def _single_gpu_prepared(model, who: str) -> torch.device:
+    """The model's device if it is one GPU and prepare_for_decode() laid the model out; raises otherwise."""
+    devices = {p.device for p in model.parameters()} | {b.device for b in model.buffers()}
+    if len(devices) != 1:
+        raise ValueError(f"{who}: the model must live on one device (found {len(devices)}); multi-GPU layouts "
+                         "are not supported")
+    dev = next(iter(devices))
+    if dev.type != "cuda":
+        raise ValueError(f"{who}: per-stream positions run in the HIP decode kernels; the model is on {dev}")
+    if not model.__dict__.get("_qz_prepared", {}).get("layer_ops"):
+        raise ValueError(f"{who}: call prepare_for_decode(model) first (the fused attention carries the positions)")
+    return dev
+
+
+class StreamSession:
+    """`batch` decode streams over `model`, each at its own position: the StaticCache
+    ([B, Hkv, max_len, D] per layer) and the static buffers a captured step reads and writes -- tok
+    [B, 1], pos [B], stop [B], limit [B] (int64), live [B] (int32), hist [B, max_len] (int64),
+    uniform [B, max_len], temperature / top_p [B] (float32), top_k [B] (int32).
+
+    hist[b] is stream b's sequence; pos[b] is the index of tok[b], its newest token, which the next
+    step feeds: that step writes k/v to cache slot pos[b], attends to slots 0..pos[b], writes its pick
+    to hist[b, pos[b] + 1] (drawn with uniform[b, pos[b]]) and advances pos[b].  A stream leaves
+    (live[b] = 0) after writing its stop token or once pos[b] reaches limit[b]; from then on the
+    step writes nothing of it, and admit() may hand its row to another prompt.  The graph is
+    captured once: positions, liveness, stop tokens, limits and sampling parameters are all read on
+    the device."""
+
+    def __init__(self, model, batch: int, max_len: int, *, graph: bool = True):
+        if batch < 1 or max_len < 2:
+            raise ValueError("StreamSession: batch must be positive and max_len at least 2")
+        self.device = _single_gpu_prepared(model, "StreamSession")
+        from transformers.cache_utils import StaticCache
+
+        self.model, self.batch, self.max_len = model, int(batch), int(max_len)
+        self.graph = bool(graph)
+        dev = self.device
+        self.cache = StaticCache(config=model.config, max_cache_len=self.max_len)
+        self._scratch = None   # admit()'s batch-1 StaticCache, made on first use
+        self.tok = torch.zeros((batch, 1), dtype=torch.int64, device=dev)
+        self.pos = torch.zeros(batch, dtype=torch.int64, device=dev)
+        self.live = torch.zeros(batch, dtype=torch.int32, device=dev)
+        self.stop = torch.full((batch,), -1, dtype=torch.int64, device=dev)
+        self.limit = torch.zeros(batch, dtype=torch.int64, device=dev)
+        # DecodeSession's shift by one: the picks write hist[b, pos[b]], the sequence wants
+        # pos[b] + 1.  One column of slack: a live stream has pos[b] + 1 <= limit[b] <= max_len - 1.
+        width = max_len + 1
+        store = torch.zeros(batch * width + 1, dtype=torch.int64, device=dev)
+        self._hist_full = store[:batch * width].view(batch, width)
+        self._hist_next = store[1:].view(batch, width)
+        self.hist = self._hist_full[:, :max_len]
+        self._uniform_full = torch.zeros((batch, width), dtype=torch.float32, device=dev)
+        self.uniform = self._uniform_full[:, :max_len]
+        self.temperature = torch.zeros(batch, dtype=torch.float32, device=dev)   # greedy until set_sampling
+        self.top_k = torch.zeros(batch, dtype=torch.int32, device=dev)
+        self.top_p = torch.ones(batch, dtype=torch.float32, device=dev)
+        self._pos_ids = self.pos.view(batch, 1)
+        # a constant 4-D bool mask: create_causal_mask hands a 4-D mask back as it is (no launch),
+        # and decode_attention_streams takes none -- visibility is j <= pos[b]
+        self._mask = torch.ones((batch, 1, 1, self.max_len), dtype=torch.bool, device=dev)
+        self._graph = None
+        self._greedy_only = True
+        self._prefilled = False
+
+    set_sampling = DecodeSession.set_sampling
+    seed = DecodeSession.seed
+
+    def _pick(self, logits: torch.Tensor, rows: slice = slice(None)) -> None:
+        r = rows
+        if self._greedy_only:
+            _ops.greedy_step_streams(logits, self._hist_next[r], self.pos[r], self.live[r], self.stop[r],
+                                     self.limit[r], self.tok[r])
+        else:
+            _ops.sample_step_streams(logits, self._hist_next[r], self.pos[r], self.live[r], self.stop[r],
+                                     self.limit[r], self.tok[r], self.temperature[r], self.top_k[r], self.top_p[r],
+                                     self._uniform_full[r])
+
+    def _limit_of(self, length: int, max_new_tokens: Optional[int]) -> int:
+        room = self.max_len - length
+        n = room if max_new_tokens is None else int(max_new_tokens)
+        if n < 1 or n > room:
+            raise ValueError(f"StreamSession: a prompt of {length} tokens has room for 1..{room} new tokens, "
+                             f"asked for {n}")
+        return length + n - 1   # the stream leaves once pos reaches it: length + n tokens in hist
+
+    @torch.inference_mode()
+    def prefill(self, input_ids: torch.Tensor, lengths, *, stop=None, max_new_tokens=None) -> None:
+        """Run right-padded prompts (input_ids [B, Smax], stream b's prompt in its first lengths[b]
+        columns) in one forward under the ordinary causal mask -- a real token never sees the pad to
+        its right -- and pick each stream's first new token from the logits at lengths[b] - 1.  The
+        pad keys left in cache slots lengths[b] .. Smax - 1 lie above pos[b]: invisible, then
+        overwritten as the stream grows.  stop: a token id per stream or one for all (None / -1:
+        none); max_new_tokens likewise (None: up to max_len)."""
+        if self._prefilled:
+            raise ValueError("StreamSession.prefill: a session is prefilled once; admit() replaces single streams")
+        if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
+            raise ValueError(f"StreamSession.prefill: input_ids must be [{self.batch}, Smax]")
+        B, Smax = input_ids.shape
+        lens = [int(x) for x in torch.as_tensor(lengths).reshape(-1).tolist()]
+        if len(lens) != B or min(lens) < 1 or max(lens) > Smax or Smax > self.max_len:
+            raise ValueError("StreamSession.prefill: one length in 1..Smax per stream, Smax <= max_len")
+        news = list(max_new_tokens) if isinstance(max_new_tokens, (list, tuple)) else [max_new_tokens] * B
+        if len(news) != B:
+            raise ValueError("StreamSession.prefill: max_new_tokens is one value or one per stream")
+        limits = [self._limit_of(n, m) for n, m in zip(lens, news)]
+        dev = self.device
+        ids = input_ids.to(dev)
+        ln = torch.tensor(lens, device=dev)
+        real = torch.arange(Smax, device=dev)[None, :] < ln[:, None]
+        self._hist_full[:, :Smax] = torch.where(real, ids, self._hist_full[:, :Smax])
+        self.pos.copy_(ln - 1)
+        self.limit.copy_(torch.tensor(limits, device=dev))
+        self.stop.copy_(_per_stream(-1 if stop is None else stop, B, torch.int64, dev, "stop"))
+        self.live.fill_(1)
+        out = self.model(input_ids=ids, past_key_values=self.cache,
+                         position_ids=torch.arange(Smax, device=dev).unsqueeze(0), use_cache=True)
+        self._pick(out.logits[torch.arange(B, device=dev), ln - 1])
+        self._prefilled = True
+
+    @torch.inference_mode()
+    def admit(self, b: int, prompt: torch.Tensor, *, stop: Optional[int] = None,
+              max_new_tokens: Optional[int] = None) -> None:
+        """Replace stream b by a new prompt (1-D) while the other streams keep their state: the
+        prompt runs eagerly at batch 1 into a scratch StaticCache, its keys and values [:S] are copied
+        into row b of every layer, and hist[b], pos[b], stop[b], limit[b], live[b] and the stream's
+        first token are written.  No recapture: the next replay reads the new state."""
+        from transformers.cache_utils import StaticCache
+
+        if not self._prefilled:
+            raise ValueError("StreamSession.admit: prefill first (it lays the cache out)")
+        if not 0 <= b < self.batch:
+            raise ValueError(f"StreamSession.admit: stream {b} outside 0..{self.batch - 1}")
+        if prompt.dim() != 1 or prompt.numel() < 1:
+            raise ValueError("StreamSession.admit: the prompt must be 1-D and not empty")
+        S = prompt.numel()
+        limit = self._limit_of(S, max_new_tokens)
+        dev = self.device
+        ids = prompt.to(dev).view(1, S)
+        if self._scratch is None:
+            self._scratch = StaticCache(config=self.model.config, max_cache_len=self.max_len)
+        else:
+            self._scratch.reset()
+        out = self.model(input_ids=ids, past_key_values=self._scratch,
+                         position_ids=torch.arange(S, device=dev).unsqueeze(0), use_cache=True)
+        for mine, theirs in zip(self.cache.layers, self._scratch.layers):
+            mine.keys[b, :, :S].copy_(theirs.keys[0, :, :S])
+            mine.values[b, :, :S].copy_(theirs.values[0, :, :S])
+        self._hist_full[b, :S] = ids[0]
+        self.pos[b] = S - 1
+        self.stop[b] = -1 if stop is None else int(stop)
+        self.limit[b] = limit
+        self.live[b] = 1    # before the pick, which writes live streams only and may retire this one at once
+        self._pick(out.logits[:, -1], slice(b, b + 1))
+
+    def _step(self) -> None:
+        lo = self.model(input_ids=self.tok, past_key_values=self.cache, position_ids=self._pos_ids,
+                        attention_mask=self._mask, use_cache=True, _qz_stream_pos=self.pos).logits
+        self._pick(lo[:, -1])
+
+    def _capture(self) -> None:
+        # two warm-up runs on a side stream, then the capture; each advances the live streams, which
+        # is undone by restoring tok, pos, live and hist (the k/v they wrote at pos + 1 lie above the
+        # restored positions: invisible, overwritten by the steps that follow).  No cache length to
+        # restore: the streams launch never touches StaticLayer.cumulative_length.
+        state = [self.tok, self.pos, self.live, self._hist_full]
+        saved = [t.clone() for t in state]
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                self._step()
+        torch.cuda.current_stream().wait_stream(s)
+        for t, v in zip(state, saved):
+            t.copy_(v)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._step()
+        for t, v in zip(state, saved):
+            t.copy_(v)
+        self._graph = g
+
+    @torch.inference_mode()
+    def step(self) -> None:
+        """One token for every live stream.  `limit` keeps each stream inside max_len on the device,
+        so there is nothing to count here; with graph=True the first call captures the step and every
+        call replays it."""
+        if not self._prefilled:
+            raise ValueError("StreamSession.step: prefill first")
+        if not self.graph:
+            self._step()
+            return
+        if self._graph is None:
+            self._capture()
+        self._graph.replay()
+
+    def alive(self) -> torch.Tensor:
+        """Which streams are live: a bool [B] on the host (one device read)."""
+        return self.live.cpu() != 0
+
+    def sequences(self) -> list:
+        """Each stream's tokens so far, hist[b, :pos[b] + 1], as 1-D int64 tensors (one read of pos)."""
+        pos = self.pos.cpu().tolist()
+        return [self.hist[b, :p + 1].clone() for b, p in enumerate(pos)]
+
+
+@torch.inference_mode()
+def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, do_sample: bool = False,
+                    temperature: Union[float, Sequence[float]] = 1.0, top_k: Union[int, Sequence[int]] = 0,
+                    top_p: Union[float, Sequence[float]] = 1.0, generator=None, eos_token_id: Optional[int] = None,
+                    graph: bool = True) -> list:
+    """generate() for prompts of different lengths: `prompts` are 1-D int64 tensors; returns one 1-D
+    int64 tensor per prompt on the model's device, the prompt followed by up to max_new_tokens picked
+    tokens of its own, ending with eos_token_id if the stream picked it.  A stream that stopped writes
+    nothing more; the host looks at `live` every STOP_CHECK_EVERY steps and returns once none is.
+    One GPU and prepare_for_decode()'s layout; anything else raises."""
+    prompts = list(prompts)
+    if not prompts or any((not isinstance(p, torch.Tensor)) or p.dim() != 1 or p.numel() < 1 for p in prompts):
+        raise ValueError("generate_ragged: prompts must be a non-empty sequence of non-empty 1-D tensors")
+    if max_new_tokens < 1:
+        raise ValueError("generate_ragged: max_new_tokens must be positive")
+    lens = [p.numel() for p in prompts]
+    B, Smax = len(prompts), max(lens)
+    sess = StreamSession(model, B, Smax + max_new_tokens, graph=graph)
+    if do_sample:
+        sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
+        sess.seed(generator)
+    ids = torch.zeros((B, Smax), dtype=torch.int64, device=sess.device)
+    for b, p in enumerate(prompts):
+        ids[b, :lens[b]] = p.to(sess.device)
+    sess.prefill(ids, lens, stop=eos_token_id, max_new_tokens=max_new_tokens)
+    n = 1
+    while n < max_new_tokens:
+        sess.step()
+        n += 1
+        if eos_token_id is not None and n % STOP_CHECK_EVERY == 0 and not bool(sess.alive().any()):
+            break
+    return sess.sequences()

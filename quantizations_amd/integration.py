@@ -290,12 +290,40 @@ def _fused_attention_forward(mod: nn.Module, orig):
     """LlamaAttention.forward (modeling_llama.py:243-281) with everything between the q/k/v
     projections and o_proj as ONE launch (layer_ops.decode_attention) when a single new token
     meets a StaticCache layer and the bool mask sdpa would get; any other call (prefill, other
-    caches, eager/flash attention, float masks) runs the original forward."""
-    from .layer_ops import decode_attention, decode_attention_supported
+    caches, eager/flash attention, float masks) runs the original forward.
+
+    `_qz_stream_pos` (int64 [B] on the GPU, generation.StreamSession): every stream has its own
+    position, so the layer runs layer_ops.decode_attention_streams -- or raises: the original
+    forward and the shared-position launch would both write every stream's k/v at one slot."""
+    from .layer_ops import (decode_attention, decode_attention_streams, decode_attention_streams_supported,
+                            decode_attention_supported)
+
+    def stream_forward(hidden_states, position_embeddings, past_key_values, pos, residual, kwargs):
+        layer = None
+        if (hidden_states.dim() == 3 and hidden_states.shape[1] == 1 and position_embeddings is not None
+                and not kwargs.get("output_attentions", False) and not mod.training):
+            layer = _static_layer(past_key_values, getattr(mod, "layer_idx", None))
+        if layer is None or layer.keys.dim() != 4 or layer.keys.shape[-1] != mod.head_dim:
+            raise ValueError("_qz_stream_pos: per-stream positions need one new token per stream against an "
+                             "initialised StaticCache layer of this module's head_dim")
+        cos, sin = position_embeddings
+        nq = layer.keys.shape[1] * (mod.config.num_attention_heads // mod.config.num_key_value_heads)
+        if not decode_attention_streams_supported(hidden_states, cos, layer.keys, layer.values, pos, nq):
+            raise ValueError("_qz_stream_pos: decode_attention_streams does not take these shapes/dtypes/layout")
+        q = mod.q_proj(hidden_states)
+        k = mod.k_proj(hidden_states)
+        v = mod.v_proj(hidden_states)
+        if q.shape[-1] != nq * mod.head_dim or k.shape[-1] != layer.keys.shape[1] * mod.head_dim:
+            raise ValueError("_qz_stream_pos: the projections' widths differ from the cache's heads")
+        out = decode_attention_streams(q, k, v, cos, sin, layer.keys, layer.values, pos, nq, mod.scaling)
+        return _project(mod.o_proj, out, residual), None
 
     def forward(hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None,
-                _qz_residual=None, **kwargs):
+                _qz_residual=None, _qz_stream_pos=None, **kwargs):
         # _qz_residual (the residual-fused decoder layer): return residual + attention output
+        if _qz_stream_pos is not None:   # taken out of kwargs: the original forward never sees it
+            return stream_forward(hidden_states, position_embeddings, past_key_values, _qz_stream_pos, _qz_residual,
+                                  kwargs)
         layer = None
         if (hidden_states.dim() == 3 and hidden_states.shape[1] == 1 and position_embeddings is not None
                 and not kwargs.get("output_attentions", False) and not mod.training

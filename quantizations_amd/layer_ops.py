@@ -11,7 +11,9 @@ projections (csrc/layer_ops.hip, C-ABI include/quantizations.h):
   post-attention RMSNorm (modeling_llama.py:317-321).
 
 ``greedy_step`` / ``sample_step`` are a decode loop's token pick with its feedback (csrc/sample.hip for the
-sampled one, which alone has a composed torch route: fp32 or CPU logits).
+sampled one, which alone has a composed torch route: fp32 or CPU logits).  ``decode_attention_streams``,
+``greedy_step_streams`` and ``sample_step_streams`` are their forms with a position per stream
+(generation.StreamSession); both streams picks have a composed torch route.
 
 None of them is in the reference (it leaves them to transformers).  They exist
 because at batch-1 decode the eager torch forms cost ~8, ~10 and 2 dependent
@@ -142,12 +144,8 @@ def silu_mul(g: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
 ATTN_CHUNK = 128  # key positions per workgroup of qz_decode_attention (csrc/layer_ops.hip)
 
 
-def decode_attention_supported(q: torch.Tensor, cos: torch.Tensor, key_cache: torch.Tensor,
-                               value_cache: torch.Tensor, mask, pos, num_heads: int) -> bool:
-    """What qz_decode_attention takes: one new token per sequence (q, or the layer input:
-    [B, 1, *]), 16-bit activations, a contiguous static cache [B, Hkv, L, D] with D in {64, 128}
-    and Hq/Hkv <= 8, a bool mask [B or 1, 1, 1, L], cos/sin [B or 1, 1, D] and an int64 position
-    on the GPU.  Metadata only: nothing is launched or allocated."""
+def _attention_operands_supported(q, cos, key_cache, value_cache, num_heads: int) -> bool:
+    """What both decode attention launches ask of the activations, the caches and cos/sin."""
     if _needs_grad(q) or not (q.is_cuda and q.dtype in (torch.float16, torch.bfloat16) and q.dim() == 3
                               and q.shape[1] == 1):
         return False
@@ -159,14 +157,46 @@ def decode_attention_supported(q: torch.Tensor, cos: torch.Tensor, key_cache: to
     for t in (key_cache, value_cache):
         if t.dtype != q.dtype or t.device != q.device or not t.is_contiguous() or t.data_ptr() % 16:
             return False
+    return (cos.dim() == 3 and cos.shape[0] in (1, B) and cos.shape[1] == 1 and cos.shape[2] == D
+            and cos.dtype == q.dtype and cos.device == q.device and cos.stride(-1) == 1)
+
+
+def decode_attention_supported(q: torch.Tensor, cos: torch.Tensor, key_cache: torch.Tensor,
+                               value_cache: torch.Tensor, mask, pos, num_heads: int) -> bool:
+    """What qz_decode_attention takes: one new token per sequence (q, or the layer input:
+    [B, 1, *]), 16-bit activations, a contiguous static cache [B, Hkv, L, D] with D in {64, 128}
+    and Hq/Hkv <= 8, a bool mask [B or 1, 1, 1, L], cos/sin [B or 1, 1, D] and an int64 position
+    on the GPU.  Metadata only: nothing is launched or allocated."""
+    if not _attention_operands_supported(q, cos, key_cache, value_cache, num_heads):
+        return False
+    B, L = key_cache.shape[0], key_cache.shape[2]
     if not (isinstance(mask, torch.Tensor) and mask.dtype == torch.bool and mask.device == q.device
             and mask.dim() == 4 and mask.shape[0] in (1, B) and mask.shape[1] == 1 and mask.shape[2] == 1
             and mask.shape[3] == L):
         return False
-    if not (cos.dim() == 3 and cos.shape[0] in (1, B) and cos.shape[1] == 1 and cos.shape[2] == D
-            and cos.dtype == q.dtype and cos.device == q.device and cos.stride(-1) == 1):
-        return False
     return (isinstance(pos, torch.Tensor) and pos.dtype == torch.int64 and pos.numel() == 1 and pos.device == q.device)
+
+
+def _attention_launch_operands(name, q, k, v, cos, sin, key_cache, num_heads):
+    """The row views, output, chunk workspace and cos/sin row stride both decode attention launches pass."""
+    B, Hkv, L, D = key_cache.shape
+    G = num_heads // Hkv
+    if q.shape[2] != num_heads * D:
+        raise ValueError(f"{name}: q width differs from num_heads * head_dim")
+    if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
+        raise ValueError(f"{name}: sin must match cos")
+    q2, k2, v2 = (t.reshape(B, -1) for t in (q, k, v))
+    k2 = k2 if k2.stride(-1) == 1 else k2.contiguous()
+    q2 = q2 if q2.stride(-1) == 1 else q2.contiguous()
+    if v2.stride(-1) != 1 or v2.stride(0) % 2 or v2.data_ptr() % 4:
+        v2 = v2.contiguous()
+    if k2.shape[1] != Hkv * D or v2.shape[1] != Hkv * D:
+        raise ValueError(f"{name}: k/v width differs from the cache's heads")
+    out = torch.empty((B, 1, num_heads * D), dtype=q.dtype, device=q.device)
+    nsplit = -(-L // ATTN_CHUNK)
+    work = torch.empty(B * Hkv * nsplit * G * (D + 2), dtype=torch.float32, device=q.device) if nsplit > 1 else None
+    cs_row = cos.stride(0) if cos.shape[0] == B and B > 1 else 0
+    return q2, k2, v2, out, work, cs_row
 
 
 def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
@@ -181,22 +211,8 @@ def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: tor
     if not decode_attention_supported(q, cos, key_cache, value_cache, mask, pos, num_heads):
         raise ValueError("decode_attention: unsupported shapes/dtypes/layout")
     B, Hkv, L, D = key_cache.shape
-    G = num_heads // Hkv
-    if q.shape[2] != num_heads * D:
-        raise ValueError("decode_attention: q width differs from num_heads * head_dim")
-    if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
-        raise ValueError("decode_attention: sin must match cos")
-    q2, k2, v2 = (t.reshape(B, -1) for t in (q, k, v))
-    k2 = k2 if k2.stride(-1) == 1 else k2.contiguous()
-    q2 = q2 if q2.stride(-1) == 1 else q2.contiguous()
-    if v2.stride(-1) != 1 or v2.stride(0) % 2 or v2.data_ptr() % 4:
-        v2 = v2.contiguous()
-    if k2.shape[1] != Hkv * D or v2.shape[1] != Hkv * D:
-        raise ValueError("decode_attention: k/v width differs from the cache's heads")
-    out = torch.empty((B, 1, num_heads * D), dtype=q.dtype, device=q.device)
-    nsplit = -(-L // ATTN_CHUNK)
-    work = torch.empty(B * Hkv * nsplit * G * (D + 2), dtype=torch.float32, device=q.device) if nsplit > 1 else None
-    cs_row = cos.stride(0) if cos.shape[0] == B and B > 1 else 0
+    q2, k2, v2, out, work, cs_row = _attention_launch_operands("decode_attention", q, k, v, cos, sin, key_cache,
+                                                               num_heads)
     mb = mask.stride(0) if mask.shape[0] == B and B > 1 else 0
     _lib.check(_lib.lib.qz_decode_attention(
         _lib.dtype_code(q.dtype), B, num_heads, Hkv, D, L, q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0),
@@ -204,6 +220,40 @@ def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: tor
         value_cache.data_ptr(), mask.data_ptr(), mb, mask.stride(3), pos.data_ptr(), arrive.data_ptr(),
         out.data_ptr(), num_heads * D, work.data_ptr() if work is not None else None, float(scale),
         _lib.stream_of(q)), "qz_decode_attention")
+    return out
+
+
+def decode_attention_streams_supported(q: torch.Tensor, cos: torch.Tensor, key_cache: torch.Tensor,
+                                       value_cache: torch.Tensor, pos, num_heads: int) -> bool:
+    """What qz_decode_attention_streams takes: decode_attention_supported's activations, caches and
+    cos/sin, no mask, and an int64 position per stream -- pos [B], contiguous, on the GPU.  Metadata
+    only: nothing is launched or allocated."""
+    if not _attention_operands_supported(q, cos, key_cache, value_cache, num_heads):
+        return False
+    return (isinstance(pos, torch.Tensor) and pos.dtype == torch.int64 and pos.dim() == 1
+            and pos.shape[0] == key_cache.shape[0] and pos.device == q.device and pos.is_contiguous())
+
+
+def decode_attention_streams(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                             key_cache: torch.Tensor, value_cache: torch.Tensor, pos: torch.Tensor, num_heads: int,
+                             scale: float) -> torch.Tensor:
+    """decode_attention with a position per stream (qz_decode_attention_streams): pos int64 [B];
+    stream b's new k/v go to cache slot pos[b] and its keys 0..pos[b] are visible.  No mask, no
+    arrival word, and pos is left as it is (greedy_step_streams / sample_step_streams advance it).
+    Each stream's output and cache rows carry the bits of decode_attention on that stream alone; a
+    position outside [0, L) gives that stream a NaN row and writes nothing of it.  Returns
+    [B, 1, Hq*D]."""
+    if not decode_attention_streams_supported(q, cos, key_cache, value_cache, pos, num_heads):
+        raise ValueError("decode_attention_streams: unsupported shapes/dtypes/layout")
+    B, Hkv, L, D = key_cache.shape
+    q2, k2, v2, out, work, cs_row = _attention_launch_operands("decode_attention_streams", q, k, v, cos, sin,
+                                                               key_cache, num_heads)
+    _lib.check(_lib.lib.qz_decode_attention_streams(
+        _lib.dtype_code(q.dtype), B, num_heads, Hkv, D, L, q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0),
+        v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cs_row, key_cache.data_ptr(),
+        value_cache.data_ptr(), pos.data_ptr(), out.data_ptr(), num_heads * D,
+        work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)),
+        "qz_decode_attention_streams")
     return out
 
 
@@ -383,3 +433,102 @@ def sample_step(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, tok
                                        uniform.data_ptr(), uniform.shape[1], hist.data_ptr(), hist.shape[1],
                                        hist.shape[1], pos.data_ptr(), tok.data_ptr(), work.data_ptr(),
                                        _lib.stream_of(logits)), "qz_sample_step")
+
+
+def _check_streams(name, logits, hist, pos, live, stop, limit, tok):
+    if logits.dim() != 2 or logits.stride(-1) != 1:
+        raise ValueError(f"{name}: logits must be [B, V] with unit element stride")
+    B = logits.shape[0]
+    for t, dt, what in ((hist, torch.int64, "hist"), (pos, torch.int64, "pos"), (tok, torch.int64, "tok"),
+                        (live, torch.int32, "live"), (stop, torch.int64, "stop"), (limit, torch.int64, "limit")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != logits.device or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be contiguous {dt} on the logits' device")
+    if hist.dim() != 2 or hist.shape[0] != B or tok.numel() != B:
+        raise ValueError(f"{name}: hist [B, H], tok [B]")
+    for t, what in ((pos, "pos"), (live, "live"), (stop, "stop"), (limit, "limit")):
+        if t.shape != (B,):
+            raise ValueError(f"{name}: {what} must be [B]")
+
+
+def _feedback_streams(token, hist, pos, live, stop, limit, tok) -> None:
+    """The per-stream feedback of qz_*_step_streams in torch ops (gather / scatter over pos, no host read)."""
+    B, H = hist.shape
+    alive = live != 0
+    p = pos.clone()
+    if H:
+        col = p.clamp(0, H - 1)[:, None]
+        inside = alive & (p >= 0) & (p < H)
+        hist.scatter_(1, col, torch.where(inside, token, hist.gather(1, col)[:, 0])[:, None])
+    tok.copy_(torch.where(alive, token, tok.view(-1)).view(tok.shape))
+    pos.copy_(torch.where(alive, p + 1, p))
+    live.copy_(torch.where(alive & ((token == stop) | (p + 1 >= limit)), torch.zeros_like(live), live))
+
+
+def _greedy_step_streams_composed(logits, hist, pos, live, stop, limit, tok) -> None:
+    _feedback_streams(logits.argmax(-1), hist, pos, live, stop, limit, tok)
+
+
+def _sample_step_streams_composed(logits, hist, pos, live, stop, limit, tok, temperature, top_k, top_p,
+                                  uniform) -> None:
+    """Each row through _sample_step_composed's rules at its own position: the uniform number is
+    gathered at pos[b] into a one-column table, the pick lands in scratch, the feedback follows."""
+    B, H = hist.shape
+    if H:
+        u = uniform.gather(1, pos.clamp(0, H - 1)[:, None])
+    else:
+        u = torch.zeros((B, 1), dtype=torch.float32, device=logits.device)
+    token = torch.zeros(B, dtype=torch.int64, device=logits.device)
+    _sample_step_composed(logits, torch.zeros((B, 1), dtype=torch.int64, device=logits.device),
+                          torch.zeros(1, dtype=torch.int64, device=logits.device), token, temperature, top_k, top_p, u)
+    _feedback_streams(token, hist, pos, live, stop, limit, tok)
+
+
+def greedy_step_streams(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, live: torch.Tensor,
+                        stop: torch.Tensor, limit: torch.Tensor, tok: torch.Tensor, *, composed: bool = False) -> None:
+    """greedy_step with the feedback per stream (qz_greedy_step_streams): pos / stop / limit int64
+    [B], live int32 [B].  A live stream b picks greedy_step's token for its row, writes
+    hist[b, pos[b]] and tok[b], advances pos[b], then clears live[b] if the token is stop[b] (-1:
+    none) or pos[b] reached limit[b]; a stream that is not live has nothing written.  CPU logits,
+    or composed=True, take the same rules in torch ops."""
+    _check_streams("greedy_step_streams", logits, hist, pos, live, stop, limit, tok)
+    B, V = logits.shape
+    if composed or not logits.is_cuda:
+        if B and V:
+            _greedy_step_streams_composed(logits, hist, pos, live, stop, limit, tok)
+        return
+    work = torch.empty(_lib.lib.qz_greedy_step_work_bytes(B, V), dtype=torch.uint8, device=logits.device)
+    _lib.check(_lib.lib.qz_greedy_step_streams(
+        logits.data_ptr(), _lib.dtype_code(logits.dtype), B, V, logits.stride(0), hist.data_ptr(), hist.shape[1],
+        hist.shape[1], pos.data_ptr(), live.data_ptr(), stop.data_ptr(), limit.data_ptr(), tok.data_ptr(),
+        work.data_ptr(), _lib.stream_of(logits)), "qz_greedy_step_streams")
+
+
+def sample_step_streams(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, live: torch.Tensor,
+                        stop: torch.Tensor, limit: torch.Tensor, tok: torch.Tensor, temperature: torch.Tensor,
+                        top_k: torch.Tensor, top_p: torch.Tensor, uniform: torch.Tensor, *,
+                        composed: bool = False) -> None:
+    """sample_step with the feedback per stream (qz_sample_step_streams): a live stream b picks what
+    sample_step picks for its row alone at pos = pos[b] (uniform[b, min(pos[b], H - 1)]), then the
+    feedback of greedy_step_streams.  fp32 or CPU logits, or composed=True, take the same rules in
+    torch ops."""
+    _check_streams("sample_step_streams", logits, hist, pos, live, stop, limit, tok)
+    B, V = logits.shape
+    for t, dt, name in ((temperature, torch.float32, "temperature"), (top_k, torch.int32, "top_k"),
+                        (top_p, torch.float32, "top_p")):
+        if t.dtype != dt or t.device != logits.device or t.shape != (B,) or not t.is_contiguous():
+            raise ValueError(f"sample_step_streams: {name} must be contiguous {dt} [B] on the logits' device")
+    if (uniform.dtype != torch.float32 or uniform.device != logits.device or uniform.shape != hist.shape
+            or not uniform.is_contiguous()):
+        raise ValueError("sample_step_streams: uniform must be contiguous float32 [B, H] on the logits' device")
+    if (composed or not logits.is_cuda or logits.dtype not in (torch.float16, torch.bfloat16)
+            or logits.stride(0) < V or B > 65535):
+        if B and V:
+            _sample_step_streams_composed(logits, hist, pos, live, stop, limit, tok, temperature, top_k, top_p,
+                                          uniform)
+        return
+    work = torch.empty(_lib.lib.qz_sample_step_work_bytes(B, V), dtype=torch.uint8, device=logits.device)
+    _lib.check(_lib.lib.qz_sample_step_streams(
+        logits.data_ptr(), _lib.dtype_code(logits.dtype), B, V, logits.stride(0), temperature.data_ptr(),
+        top_k.data_ptr(), top_p.data_ptr(), uniform.data_ptr(), uniform.shape[1], hist.data_ptr(), hist.shape[1],
+        hist.shape[1], pos.data_ptr(), live.data_ptr(), stop.data_ptr(), limit.data_ptr(), tok.data_ptr(),
+        work.data_ptr(), _lib.stream_of(logits)), "qz_sample_step_streams")

@@ -354,6 +354,24 @@ int qz_decode_attention_streams(int dtype, int B, int Hq, int Hkv, int D, int L,
                                 const void *sin, long long cs_row, void *k_cache, void *v_cache,
                                 const long long *pos, void *out, long long out_row, float *work, float scale,
                                 void *stream);
+/* qz_decode_attention_streams for T new tokens per stream, causal among themselves (a window of
+ * drafts to verify): q/out have B*T rows, k/v B*T rows, cos/sin one row per token row (row stride
+ * cs_row); token row r = b*T + i sits at position p_b + i with p_b = pos[b] (int64 [B], read only).
+ *   - the rotated k and the v of row (b, i) go to slot p_b + i of cache row b, and the row sees keys
+ *     0 .. p_b + i of that cache row, the window's earlier rows included;
+ *   - out and the caches are bit-identical to T successive qz_decode_attention_streams calls on
+ *     stream b alone at positions p_b, p_b + 1, ...: a token's result does not depend on i;
+ *   - a row with p_b + i >= L writes nothing and is NaN, that row only; p_b < 0 makes all T rows of
+ *     stream b NaN and writes nothing of it; other streams are unaffected.
+ * Launches: one that rotates and stores the B*T new keys and values, the attention (which reads
+ * slot p_b + i from the cache like any other key), and the combine when L > 128.
+ *   work: L > 128 only, B*T*Hkv*ceil(L/128)*(Hq/Hkv)*(D+2) floats; B*T <= 65535 (QZ_ERR_SHAPE).
+ * Every other operand and the status codes are qz_decode_attention_streams'. */
+int qz_decode_attention_verify(int dtype, int B, int T, int Hq, int Hkv, int D, int L, const void *q, long long q_row,
+                               const void *k, long long k_row, const void *v, long long v_row, const void *cos,
+                               const void *sin, long long cs_row, void *k_cache, void *v_cache,
+                               const long long *pos, void *out, long long out_row, float *work, float scale,
+                               void *stream);
 
 /* Decode-step glue of the host model (transformers' LlamaModel.forward), one launch each in place
  * of the small torch kernels it issues per step.  Not part of the Linear4bit path; the
@@ -413,6 +431,29 @@ int qz_sample_step_streams(const void *logits, int dtype, int B, long long V, lo
                            long long uniform_row, long long *hist, long long hist_row, long long hist_len,
                            long long *pos, int *live, const long long *stop, const long long *limit,
                            long long *tok, void *work, void *stream);
+/* qz_verify_step_streams: the greedy pick that accepts drafts.  logits [B*T, V] (row stride `row`):
+ *   row b*T + i is the model's output after tok[b, 0..i]; tok int64 [B, T] contiguous, column 0 the
+ *   token that was fed, columns 1.. the drafts.  g_i = qz_greedy_step's pick of row b*T + i.  A live
+ *   stream does what successive qz_greedy_step_streams calls would:
+ *     for i = 0, 1, ...: hist[b, pos[b]] = g_i; pos[b] += 1;
+ *                        g_i == stop[b] or pos[b] >= limit[b]: live[b] = 0, end;
+ *                        i == T - 1 or tok[b, i + 1] != g_i: end
+ *   then tok[b, 0] = the last token emitted and accepted[b] (int32 [B]) = the number emitted, 1..T.
+ *   A stream that is not live has accepted[b] = 0 and nothing else written.  Emitted row i has
+ *   pos + i + 1 <= limit[b]: with limit[b] <= L - 1 no row past the cache is ever emitted.
+ *   T <= 16, B*T <= 65535 (QZ_ERR_SHAPE); F16/BF16/F32; work: qz_greedy_step_work_bytes(B*T, V).
+ * qz_ngram_draft: the prompt-lookup drafter, one workgroup per stream.  s = hist[b, 0..p], p = pos[b]
+ *   (s[p] is tok[b, 0]).  For n = ngram_max .. 1 with n <= p: the largest m with m + n <= p and
+ *   s[m .. m+n-1] == s[p-n+1 .. p]; the first n that has one wins.  With e = s followed by the
+ *   drafts written so far, tok[b, 1 + i] = e[m + n + i] (the index is below p + 1 + i); with no
+ *   match, or p outside [0, hist_len), every draft is tok[b, 0].  Also writes pos_ids[b, i] = p + i
+ *   (int64 [B, T]).  1 <= ngram_max <= 4 (QZ_ERR_ARG), T <= 16 (QZ_ERR_SHAPE). */
+int qz_verify_step_streams(const void *logits, int dtype, int B, int T, long long V, long long row, long long *hist,
+                           long long hist_row, long long hist_len, long long *pos, int *live,
+                           const long long *stop, const long long *limit, long long *tok, int *accepted,
+                           void *work, void *stream);
+int qz_ngram_draft(int B, int T, int ngram_max, const long long *hist, long long hist_row, long long hist_len,
+                   const long long *pos, long long *tok, long long *pos_ids, void *stream);
 /* qz_gemv_dense: the model's fp16/bf16 lm_head for one decode token (transformers keeps it
  *   unquantised): y[m] = sum_k W[m*K + k] x[k] for m < M, fp32 accumulation, rounded once to
  *   dtype; K in {4096, 8192}, W and x 16-B aligned (else QZ_ERR_SHAPE, nothing launched). */

@@ -23,6 +23,7 @@ from .autograd import MatMul4Bit  # noqa: F401
 from .modules import Linear4bit, matmul_4bit  # noqa: F401
 from .generation import (  # noqa: F401
     DecodeSession,
+    SpeculativeSession,
     StreamSession,
     generate,
     generate_ragged,

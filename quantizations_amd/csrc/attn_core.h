@@ -118,9 +118,15 @@ template <int D> struct AttnLds {
 // STREAMS (qz_decode_attention_streams): p is a.pos[b], the stream's own position, and the mask is
 // j <= p computed here; everything after those two reads is the same code, so a stream's row
 // carries the bits of a B = 1 launch with that mask and position.
-template <int DT, int D, bool STREAMS = false>
+// VERIFY (qz_decode_attention_verify, with STREAMS): `b` is the token row (q, cos / sin, out and the
+// partials), `cb` the cache row it attends to and `pv` its position; the new keys and values are in
+// the cache already (k_verify_kv_write, the launch before), so nothing is rotated or written here
+// but q, and slot pv is read from the cache like any other key -- the bits s_kn / s_vn carry in the
+// streams kernel.  Everything after the loads is the same code again.
+template <int DT, int D, bool STREAMS = false, bool VERIFY = false>
 __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, int split, int hq, int b,
-                                                      const AttnLds<D> &S) {
+                                                      const AttnLds<D> &S, int cb = 0, long long pv = 0) {
+  static_assert(STREAMS || !VERIFY, "the verify form computes its mask from the position");
   constexpr int ES = DT == QZ_DT_F32 ? 4 : 2;
   static_assert(ES == 2, "16-bit activations and caches");
   constexpr int H2 = D / 2;      // rotary half; also the share of a row one thread dots
@@ -135,7 +141,7 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
   const int G = a.G, L = a.L;
   const int h = hq / G, gq = hq - h * G;                     // kv head, query head within it
   const int j0 = split * kAttnChunk;
-  const long long crow = ((long long)b * a.Hkv + h) * L;     // first cache row of (b, h)
+  const long long crow = ((long long)(VERIFY ? cb : b) * a.Hkv + h) * L;   // first cache row of (b, h)
   const int pos_i = t & (kAttnChunk - 1), half = t >> 7;     // this thread's key position / row half
   const long long j = j0 + pos_i;
   const bool in_l = j < L;
@@ -146,7 +152,7 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
   //    position j -- whatever the mask says (a masked row is dropped after it arrives) -- for
   //    caches up to kAttnSpecL positions; a longer cache is read after its mask, so a long
   //    static cache early in a sequence does not stream its masked rows.
-  const long long p = STREAMS ? a.pos[b] : *a.pos;
+  const long long p = VERIFY ? pv : STREAMS ? a.pos[b] : *a.pos;
   const bool rt = t < H2;
   float x1 = 0.f, x2 = 0.f, c1 = 0.f, c2 = 0.f, s1 = 0.f, s2 = 0.f, k1 = 0.f, k2 = 0.f;
   uint32_t vnew = 0u;
@@ -157,8 +163,10 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
     const char *kb = reinterpret_cast<const char *>(a.k) + ((long long)b * a.ks + (long long)h * D) * ES;
     const char *vb = reinterpret_cast<const char *>(a.v) + ((long long)b * a.vs + (long long)h * D) * ES;
     x1 = load_f32<DT>(qb, t); x2 = load_f32<DT>(qb, t + H2);
-    k1 = load_f32<DT>(kb, t); k2 = load_f32<DT>(kb, t + H2);
-    vnew = reinterpret_cast<const uint32_t *>(vb)[t];  // elements 2t, 2t + 1
+    if constexpr (!VERIFY) {
+      k1 = load_f32<DT>(kb, t); k2 = load_f32<DT>(kb, t + H2);
+      vnew = reinterpret_cast<const uint32_t *>(vb)[t];  // elements 2t, 2t + 1
+    }
     c1 = load_f32<DT>(cb, t); c2 = load_f32<DT>(cb, t + H2);
     s1 = load_f32<DT>(sb, t); s2 = load_f32<DT>(sb, t + H2);
   }
@@ -188,7 +196,7 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
     lo = from_bits<DT>(bits_dt<DT>(__fadd_rn(round_dt<DT>(__fmul_rn(u1, c1)), round_dt<DT>(__fmul_rn(-u2, s1)))));
     hi = from_bits<DT>(bits_dt<DT>(__fadd_rn(round_dt<DT>(__fmul_rn(u2, c2)), round_dt<DT>(__fmul_rn(u1, s2)))));
   };
-  const bool mine = p >= j0 && p < j0 + kAttnChunk && p < L;  // this chunk holds the new token
+  const bool mine = !VERIFY && p >= j0 && p < j0 + kAttnChunk && p < L;  // this chunk holds the new token
   if (rt) {
     float lo, hi;
     rope(x1, x2, lo, hi);
@@ -222,14 +230,14 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
   //    and stages that half of the position's v row in LDS (zeros where masked / past L)
   {
     const bool ok = mk != 0;
-    if (!spec && ok && j != p) {  // long cache: the rows the mask keeps, read now
+    if (!spec && ok && (VERIFY || j != p)) {  // long cache: the rows the mask keeps, read now
 #pragma unroll
       for (int i = 0; i < NW / 4; ++i) kr[i] = kp[i];
 #pragma unroll
       for (int i = 0; i < NW / 4; ++i) vr[i] = vp[i];
     }
     uint32_t kw[NW], vw[NW];
-    if (ok && j == p) {
+    if (!VERIFY && ok && j == p) {
 #pragma unroll
       for (int i = 0; i < NW; ++i) { kw[i] = s_kn[half * NW + i]; vw[i] = s_vn[half * NW + i]; }
     } else {

@@ -276,6 +276,82 @@ __global__ __launch_bounds__(256) void k_decode_attn_streams(DecodeAttnArgs a) {
   decode_attn_head<DT, D, true>(a, split, hq, b, S);
 }
 
+// T new tokens per stream, causal among themselves (qz_decode_attention_verify): token row r = b T + i
+// sits at position pos[b] + i of cache row b.  Two launches.  k_verify_kv_write rotates the B T new
+// keys (the head's own expression, so the cache receives the bits a streams launch at that position
+// stores) and copies the new values into their slots; k_decode_attn_verify then runs the streams
+// head per token row against cache row b with no cache write: slot pos[b] + i and the window's
+// earlier rows are read like any other key.  The loads come after the write launch, so the early
+// loads of a cache up to kAttnSpecL stay legal.  A row with pos[b] < 0 or pos[b] + i >= L writes
+// nothing and is NaN (the streams kernel's rule at that position); a chunk that starts above the
+// row's position leaves the neutral partial.
+struct VerifyKvArgs {
+  const void *k, *v;         // [B T, Hkv D], row r at r * {ks, vs} elements
+  long long ks, vs;
+  const void *cos, *sin;     // row r at r * cs
+  long long cs;
+  void *kc, *vc;             // [B, Hkv, L, D]
+  const long long *pos;      // [B]
+  int Hkv, L, T;
+};
+// grid (Hkv, B T), 64 threads: thread t < D / 2 rotates the pair (t, t + D / 2) and copies one word of v
+template <int DT, int D>
+__global__ __launch_bounds__(64) void k_verify_kv_write(VerifyKvArgs a) {
+  constexpr int ES = 2, H2 = D / 2;
+  const int t = threadIdx.x, h = blockIdx.x, r = blockIdx.y;
+  const int b = r / a.T;
+  const long long pb = a.pos[b];
+  if (t >= H2 || pb < 0 || pb >= a.L) return;
+  const long long p = pb + (r - b * a.T);
+  if (p >= a.L) return;
+  const char *cb = reinterpret_cast<const char *>(a.cos) + (long long)r * a.cs * ES;
+  const char *sb = reinterpret_cast<const char *>(a.sin) + (long long)r * a.cs * ES;
+  const char *kb = reinterpret_cast<const char *>(a.k) + ((long long)r * a.ks + (long long)h * D) * ES;
+  const char *vb = reinterpret_cast<const char *>(a.v) + ((long long)r * a.vs + (long long)h * D) * ES;
+  const float k1 = load_f32<DT>(kb, t), k2 = load_f32<DT>(kb, t + H2);
+  const uint32_t vnew = reinterpret_cast<const uint32_t *>(vb)[t];
+  const float c1 = load_f32<DT>(cb, t), c2 = load_f32<DT>(cb, t + H2);
+  const float s1 = load_f32<DT>(sb, t), s2 = load_f32<DT>(sb, t + H2);
+  // decode_attn_head's rope(): k*cos + cat(-k2, k1)*sin, every torch op rounded to the storage dtype
+  const float lo = from_bits<DT>(bits_dt<DT>(__fadd_rn(round_dt<DT>(__fmul_rn(k1, c1)), round_dt<DT>(__fmul_rn(-k2, s1)))));
+  const float hi = from_bits<DT>(bits_dt<DT>(__fadd_rn(round_dt<DT>(__fmul_rn(k2, c2)), round_dt<DT>(__fmul_rn(k1, s2)))));
+  const long long slot = (((long long)b * a.Hkv + h) * a.L + p) * D * ES;
+  char *kd = reinterpret_cast<char *>(a.kc) + slot;
+  char *vd = reinterpret_cast<char *>(a.vc) + slot;
+  store_f32<DT>(kd, t, lo);
+  store_f32<DT>(kd, t + H2, hi);
+  reinterpret_cast<uint32_t *>(vd)[t] = vnew;
+}
+
+// grid (nsplit, Hq, B T): k_decode_attn_streams with the position of token row r = blockIdx.z
+template <int DT, int D>
+__global__ __launch_bounds__(256) void k_decode_attn_verify(DecodeAttnArgs a, int T) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_v[kAttnChunk * (D / 2)];
+  __shared__ __attribute__((aligned(16))) unsigned char s_small[AttnLds<D>::kSmallBytes];
+  const int split = blockIdx.x, hq = blockIdx.y, r = blockIdx.z, t = threadIdx.x;
+  const int b = r / T;
+  const long long pb = a.pos[b];
+  const bool bad = pb < 0 || pb >= a.L || pb + (r - b * T) >= a.L;
+  const long long p = bad ? 0 : pb + (r - b * T);
+  if (bad || (long long)split * kAttnChunk > p) {   // uniform over the workgroup
+    if (t < D) {
+      const float fill = bad ? __builtin_nanf("") : 0.0f;
+      if (a.nsplit == 1) {
+        char *ob = reinterpret_cast<char *>(a.out) + ((long long)r * a.os + (long long)hq * D) * 2;
+        store_f32<DT>(ob, t, fill);
+      } else {
+        const int h = hq / a.G, gq = hq - h * a.G;
+        float *pp = a.part + ((((long long)r * a.Hkv + h) * a.nsplit + split) * a.G + gq) * (D + 2);
+        pp[t] = fill;
+        if (t == 0) { pp[D] = -INFINITY; pp[D + 1] = 0.0f; }
+      }
+    }
+    return;
+  }
+  const AttnLds<D> S{s_v, s_small};
+  decode_attn_head<DT, D, true, true>(a, split, hq, r, S, b, p);
+}
+
 // nsplit > 1: merge the chunk partials of one (b, kv head) -- out = sum_s e^(m_s - M) o_s /
 // sum_s e^(m_s - M) l_s with M = max_s m_s; empty chunks (m_s = -inf) weigh nothing
 template <int DT, int D>
@@ -309,6 +385,17 @@ template <int DT, int D>
 void launch_decode_attn_streams(const DecodeAttnArgs &a, int B, hipStream_t s) {
   hipLaunchKernelGGL((k_decode_attn_streams<DT, D>), dim3(a.nsplit, a.Hkv * a.G, B), dim3(256), 0, s, a);
   if (a.nsplit > 1) hipLaunchKernelGGL((k_decode_attn_combine<DT, D>), dim3(a.Hkv, B), dim3(256), 0, s, a);
+}
+
+// `a` holds the B T token rows as its batch (out, the partials and the combine go by token row)
+template <int DT, int D>
+void launch_decode_attn_verify(const DecodeAttnArgs &a, int B, int T, hipStream_t s) {
+  VerifyKvArgs w{};
+  w.k = a.k; w.v = a.v; w.ks = a.ks; w.vs = a.vs; w.cos = a.cos; w.sin = a.sin; w.cs = a.cs;
+  w.kc = a.kc; w.vc = a.vc; w.pos = a.pos; w.Hkv = a.Hkv; w.L = a.L; w.T = T;
+  hipLaunchKernelGGL((k_verify_kv_write<DT, D>), dim3(a.Hkv, B * T), dim3(64), 0, s, w);
+  hipLaunchKernelGGL((k_decode_attn_verify<DT, D>), dim3(a.nsplit, a.Hkv * a.G, B * T), dim3(256), 0, s, a, T);
+  if (a.nsplit > 1) hipLaunchKernelGGL((k_decode_attn_combine<DT, D>), dim3(a.Hkv, B * T), dim3(256), 0, s, a);
 }
 
 template <int DT, bool ADD>
@@ -509,6 +596,93 @@ __global__ __launch_bounds__(256) void k_greedy_final(int B, long long V, int nb
   if (tid == 0 && !live) *pos = p0 + 1;
 }
 
+// The greedy pick that accepts drafts (qz_verify_step_streams): logits row b T + i is what the model
+// says after tok[b, 0..i]; k_greedy_partial reduces the B T rows as it does any batch, then one
+// workgroup per stream reduces its T rows' partials to the picks g_0..g_{T-1} and thread 0 does what
+// successive k_greedy_final calls would do for as long as the next draft is the token just picked.
+constexpr int kVerifyMaxT = 16;
+__global__ __launch_bounds__(256) void k_verify_final(int T, long long V, int nb, const float *pv, const long long *pi,
+                                                      long long *hist, long long hist_row, long long hist_len,
+                                                      long long *pos, long long *tok, int *live,
+                                                      const long long *stop, const long long *limit, int *accepted) {
+  __shared__ float s_v[4];
+  __shared__ long long s_i[4];
+  __shared__ long long s_g[kVerifyMaxT];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  for (int i = 0; i < T; ++i) {
+    const size_t r = (size_t)b * T + i;
+    float best = -__builtin_inff();
+    long long bi = V;
+    for (int c = tid; c < nb; c += 256) {
+      const float v = pv[r * nb + c];
+      const long long j = pi[r * nb + c];
+      if (j != V && (bi == V || greedy_better(v, j, best, bi))) { best = v; bi = j; }
+    }
+    greedy_reduce_wg(best, bi, V, s_v, s_i);
+    if (tid == 0) s_g[i] = bi;
+  }
+  if (tid != 0) return;
+  if (live[b] == 0) { accepted[b] = 0; return; }
+  long long p = pos[b], g = 0;
+  int n = 0;
+  for (int i = 0; i < T; ++i) {
+    g = s_g[i];
+    if (p >= 0 && p < hist_len) hist[(size_t)b * hist_row + p] = g;
+    p += 1;
+    n += 1;
+    if (g == stop[b] || p >= limit[b]) { live[b] = 0; break; }
+    if (i == T - 1 || tok[(size_t)b * T + i + 1] != g) break;
+  }
+  tok[(size_t)b * T] = g;
+  pos[b] = p;
+  accepted[b] = n;
+}
+
+// The prompt-lookup drafter (qz_ngram_draft): one workgroup per stream.  s = hist[b, 0..p], p = pos[b].
+// For n = ngram_max .. 1 (n <= p) the threads try every start m <= p - n of an earlier copy of the
+// last n tokens and keep the largest; the first n with a match wins.  Thread 0 then copies what
+// followed that copy, running on into the drafts themselves (index m + n + i < p + 1 + i).
+__global__ __launch_bounds__(256) void k_ngram_draft(int T, int ngram_max, const long long *hist, long long hist_row,
+                                                     long long hist_len, const long long *pos, long long *tok,
+                                                     long long *pos_ids) {
+  __shared__ int s_best;
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const long long p64 = pos[b];
+  if (tid < T) pos_ids[(size_t)b * T + tid] = p64 + tid;
+  const long long *s = hist + (size_t)b * hist_row;
+  long long *tb = tok + (size_t)b * T;
+  int m = -1, n = 0;
+  if (p64 >= 1 && p64 < hist_len) {
+    const int p = (int)p64;
+    for (n = ngram_max < p ? ngram_max : p; n >= 1; --n) {
+      if (tid == 0) s_best = -1;
+      __syncthreads();
+      int mine = -1;
+      for (int c = tid; c + n <= p; c += 256) {
+        bool eq = true;
+        for (int e = 0; e < n; ++e) eq = eq && s[c + e] == s[p - n + 1 + e];
+        if (eq) mine = c;   // increasing c: the last match of this thread
+      }
+      if (mine >= 0) atomicMax(&s_best, mine);
+      __syncthreads();
+      m = s_best;
+      __syncthreads();
+      if (m >= 0) break;
+    }
+  }
+  if (tid != 0) return;
+  if (m < 0) {
+    const long long t0 = tb[0];
+    for (int i = 1; i < T; ++i) tb[i] = t0;
+    return;
+  }
+  const long long p = p64;
+  for (int i = 0; i + 1 < T; ++i) {
+    const long long e = (long long)m + n + i;
+    tb[1 + i] = e <= p ? s[e] : tb[e - p];   // e - p - 1 drafts back: column 1 + (e - p - 1)
+  }
+}
+
 // ---- the host model's fp16 / bf16 lm_head for one decode token (not 4-bit: transformers keeps it
 // in the model dtype): y[m] = sum_k W[m, k] x[k], fp32 accumulation, rounded once.  Each wave owns
 // R rows; lane l reads the 16-B chunks l, l + 64, ... of a row (KCH = K / 512 of them) with
@@ -694,6 +868,24 @@ extern "C" int qz_decode_attention_streams(int dtype, int B, int Hq, int Hkv, in
   return (int)hipGetLastError();
 }
 
+extern "C" int qz_decode_attention_verify(int dtype, int B, int T, int Hq, int Hkv, int D, int L, const void *q,
+                                          long long q_row, const void *k, long long k_row, const void *v,
+                                          long long v_row, const void *cos, const void *sin, long long cs_row,
+                                          void *k_cache, void *v_cache, const long long *pos, void *out,
+                                          long long out_row, float *work, float scale, void *stream) {
+  if (B < 0 || T < 0 || Hq < 0 || Hkv < 0 || D < 0 || L < 0) return QZ_ERR_ARG;
+  if (B == 0 || T == 0 || Hq == 0) return 0;
+  if ((long long)B * T > 65535) return QZ_ERR_SHAPE;   // token rows are a grid dimension
+  DecodeAttnArgs a{};
+  const int rc = decode_attn_args(dtype, B * T, Hq, Hkv, D, L, q, q_row, k, k_row, v, v_row, cos, sin, cs_row, k_cache,
+                                  v_cache, true, pos, out, out_row, work, scale, a);
+  if (rc <= 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == QZ_DT_F16) D == 64 ? launch_decode_attn_verify<QZ_DT_F16, 64>(a, B, T, s) : launch_decode_attn_verify<QZ_DT_F16, 128>(a, B, T, s);
+  else D == 64 ? launch_decode_attn_verify<QZ_DT_BF16, 64>(a, B, T, s) : launch_decode_attn_verify<QZ_DT_BF16, 128>(a, B, T, s);
+  return (int)hipGetLastError();
+}
+
 extern "C" int qz_decode_mask(const long long *q_offset, int B, int L, void *mask, void *stream) {
   if (B < 0 || L < 0) return QZ_ERR_ARG;
   if (B == 0 || L == 0) return 0;
@@ -779,6 +971,49 @@ extern "C" int qz_greedy_step_streams(const void *logits, int dtype, int B, long
     return QZ_ERR_ARG;
   return greedy_step_launch(logits, dtype, B, V, row, hist, hist_row, hist_len, pos, tok, live, stop, limit, work,
                             stream);
+}
+
+extern "C" int qz_verify_step_streams(const void *logits, int dtype, int B, int T, long long V, long long row,
+                                      long long *hist, long long hist_row, long long hist_len, long long *pos,
+                                      int *live, const long long *stop, const long long *limit, long long *tok,
+                                      int *accepted, void *work, void *stream) {
+  if (B < 0 || T < 0 || V < 0 || row < 0 || hist_row < 0 || hist_len < 0) return QZ_ERR_ARG;
+  if (B == 0 || T == 0) return 0;
+  if (V == 0 || !logits || !hist || !pos || !live || !stop || !limit || !tok || !accepted || !work || row < V ||
+      (B > 1 && hist_row < hist_len))
+    return QZ_ERR_ARG;
+  if (T > kVerifyMaxT || (long long)B * T > 65535) return QZ_ERR_SHAPE;
+  const long long nbl = (V + kGreedyChunk - 1) / kGreedyChunk;
+  if (nbl > 0x7FFFFFFFLL) return QZ_ERR_SHAPE;
+  if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16 && dtype != QZ_DT_F32) return QZ_ERR_DTYPE;
+  const int nb = (int)nbl, R = B * T;
+  float *pv = reinterpret_cast<float *>(work);
+  long long *pi = reinterpret_cast<long long *>(reinterpret_cast<unsigned char *>(work) + (size_t)R * nb * 8);
+  hipStream_t s = (hipStream_t)stream;
+  const int esz = dtype == QZ_DT_F32 ? 4 : 2;
+  const bool vec = (V * esz) % 16 == 0 && (row * esz) % 16 == 0 && (uintptr_t)logits % 16 == 0;
+  const dim3 g((unsigned)nb, (unsigned)R);
+  switch (dtype) {
+    case QZ_DT_F16: hipLaunchKernelGGL((k_greedy_partial<QZ_DT_F16>), g, dim3(256), 0, s, logits, row, V, nb, pv, pi, vec); break;
+    case QZ_DT_BF16: hipLaunchKernelGGL((k_greedy_partial<QZ_DT_BF16>), g, dim3(256), 0, s, logits, row, V, nb, pv, pi, vec); break;
+    default: hipLaunchKernelGGL((k_greedy_partial<QZ_DT_F32>), g, dim3(256), 0, s, logits, row, V, nb, pv, pi, vec); break;
+  }
+  hipLaunchKernelGGL(k_verify_final, dim3((unsigned)B), dim3(256), 0, s, T, V, nb, pv, pi, hist, hist_row, hist_len, pos,
+                     tok, live, stop, limit, accepted);
+  return (int)hipGetLastError();
+}
+
+extern "C" int qz_ngram_draft(int B, int T, int ngram_max, const long long *hist, long long hist_row,
+                              long long hist_len, const long long *pos, long long *tok, long long *pos_ids,
+                              void *stream) {
+  if (B < 0 || T < 0 || hist_row < 0 || hist_len < 0) return QZ_ERR_ARG;
+  if (B == 0 || T == 0) return 0;
+  if (!hist || !pos || !tok || !pos_ids || (B > 1 && hist_row < hist_len)) return QZ_ERR_ARG;
+  if (ngram_max < 1 || ngram_max > 4) return QZ_ERR_ARG;
+  if (T > kVerifyMaxT || B > 65535 || hist_len > 0x7FFFFFFFLL) return QZ_ERR_SHAPE;
+  hipLaunchKernelGGL(k_ngram_draft, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, T, ngram_max, hist, hist_row,
+                     hist_len, pos, tok, pos_ids);
+  return (int)hipGetLastError();
 }
 
 extern "C" int qz_gemv_dense(int M, int K, const void *x, int dtype, const void *W, void *y, void *stream) {

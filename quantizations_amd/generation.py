@@ -6,8 +6,9 @@ The pick is layer_ops.sample_step -- per-stream temperature, top-k and top-p rea
 a replay follows set_sampling() -- or layer_ops.greedy_step when every stream is greedy at capture.
 DecodeSession / generate() take equal-length prompts and move every stream together; StreamSession
 / generate_ragged() keep a position per stream on the device (prompts of different lengths, a
-finished stream's row handed to the next prompt without recapturing).  One GPU only; no penalties,
-no beams.
+finished stream's row handed to the next prompt without recapturing).  SpeculativeSession /
+prompt_lookup_num_tokens= verify prompt-lookup drafts: several greedy tokens per stream and step, the
+same tokens in fewer reads of the weights.  One GPU only; no penalties, no beams.
 """
 from __future__ import annotations
 
@@ -206,18 +207,32 @@ class DecodeSession:
 def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: bool = False,
              temperature: Union[float, Sequence[float]] = 1.0, top_k: Union[int, Sequence[int]] = 0,
              top_p: Union[float, Sequence[float]] = 1.0, generator=None, eos_token_id: Optional[int] = None,
-             attention_mask: Optional[torch.Tensor] = None, graph: bool = True) -> torch.Tensor:
+             attention_mask: Optional[torch.Tensor] = None, graph: bool = True,
+             prompt_lookup_num_tokens: Optional[int] = None,
+             max_matching_ngram_size: Optional[int] = None) -> torch.Tensor:
     """input_ids [B, S] (equal-length prompts) followed by up to max_new_tokens picked tokens per
     stream: greedy, or with do_sample temperature / top_k / top_p (scalars or one per stream; a
     temperature <= 0 keeps that stream greedy) drawn from `generator` (a torch.Generator or a seed).
     With eos_token_id the history is looked at on the host every 16 steps: a stream's tokens after
     its first EOS are that EOS, and the call returns once every stream has stopped.  Returns int64
-    [B, S + new] on the model's device."""
+    [B, S + new] on the model's device.
+    prompt_lookup_num_tokens (transformers' name): verify that many prompt-lookup drafts per stream
+    and step in a SpeculativeSession (suffixes of up to max_matching_ngram_size tokens, default 2).
+    Greedy only; it needs prepare_for_decode()'s layout on one GPU; the result has the shape and the
+    EOS fill the plain call defines."""
     if input_ids.dim() != 2:
         raise ValueError("generate: input_ids must be [B, S]")
     B, S = input_ids.shape
+    if prompt_lookup_num_tokens is None and max_matching_ngram_size is not None:
+        raise ValueError("generate: max_matching_ngram_size needs prompt_lookup_num_tokens")
+    if prompt_lookup_num_tokens is not None and do_sample:
+        raise ValueError("generate: prompt_lookup_num_tokens verifies drafts against the greedy token; "
+                         "do_sample is not supported with it")
     if max_new_tokens < 1:
         return input_ids.clone()
+    if prompt_lookup_num_tokens is not None:
+        return _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attention_mask, graph,
+                                     prompt_lookup_num_tokens, max_matching_ngram_size)
     sess = DecodeSession(model, B, S + max_new_tokens, graph=graph)
     if do_sample:
         sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
@@ -398,12 +413,16 @@ class StreamSession:
                         attention_mask=self._mask, use_cache=True, _qz_stream_pos=self.pos).logits
         self._pick(lo[:, -1])
 
+    def _step_state(self) -> list:
+        """What a step writes besides the cache: _capture() puts it back after its warm-up runs."""
+        return [self.tok, self.pos, self.live, self._hist_full]
+
     def _capture(self) -> None:
         # two warm-up runs on a side stream, then the capture; each advances the live streams, which
         # is undone by restoring tok, pos, live and hist (the k/v they wrote at pos + 1 lie above the
         # restored positions: invisible, overwritten by the steps that follow).  No cache length to
         # restore: the streams launch never touches StaticLayer.cumulative_length.
-        state = [self.tok, self.pos, self.live, self._hist_full]
+        state = self._step_state()
         saved = [t.clone() for t in state]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -444,16 +463,141 @@ class StreamSession:
         return [self.hist[b, :p + 1].clone() for b, p in enumerate(pos)]
 
 
+SPECULATIVE_CHECK_EVERY = 4   # speculative generate: steps between host looks at `live`
+PROMPT_LOOKUP_NGRAM = 2       # transformers' default max_matching_ngram_size
+
+
+class SpeculativeSession(StreamSession):
+    """StreamSession that verifies draft_tokens drafts per stream and step, greedy only.  tok is
+    [B, T] with T = draft_tokens + 1: column 0 is the stream's newest token, columns 1.. are drafts for
+    the tokens after it.  A step runs the model on all B T rows in one read of the weights (the window
+    is causal within a stream: layer_ops.decode_attention_verify), picks the greedy token of every
+    row, and emits row 0's pick and then each further row's pick for as long as the draft that row was
+    fed is the token just emitted (layer_ops.verify_step_streams): 1..T tokens per live stream,
+    accepted [B] of them.  The tokens are those of StreamSession whatever the drafts were, because
+    every launch of the step gives a token the same bits in whichever row it sits.  Rejected rows
+    left k/v above the new pos[b]: invisible, overwritten later.  A row past the cache end is NaN and
+    is never emitted (pos[b] + i + 1 <= limit[b] <= max_len - 1 for an emitted row i).
+
+    _draft() fills tok[:, 1:] and pos_ids [B, T] = pos[b] + i for the next step; here it is the
+    prompt-lookup drafter layer_ops.ngram_draft over the stream's own history with suffixes of up to
+    `ngram` tokens.  A subclass may replace it with anything that runs on the device and writes token
+    ids of the vocabulary for every stream, live or not (the embedding looks all B T rows up).
+    batch * T is at most core.MT_MAX_TOKENS (the multi-token 4-bit kernel's rows)."""
+
+    def __init__(self, model, batch: int, max_len: int, *, draft_tokens: int = 3, ngram: int = 3, graph: bool = True):
+        from .core import MT_MAX_TOKENS
+
+        if int(draft_tokens) < 1:
+            raise ValueError("SpeculativeSession: draft_tokens must be at least 1")
+        if not 1 <= int(ngram) <= _ops.NGRAM_MAX:
+            raise ValueError(f"SpeculativeSession: ngram must be in 1..{_ops.NGRAM_MAX}")
+        T = int(draft_tokens) + 1
+        if batch * T > MT_MAX_TOKENS:
+            raise ValueError(f"SpeculativeSession: batch * (draft_tokens + 1) = {batch * T} rows per step, the "
+                             f"multi-token kernels take {MT_MAX_TOKENS}")
+        super().__init__(model, batch, max_len, graph=graph)
+        dev = self.device
+        self.T, self.ngram = T, int(ngram)
+        self.tok = torch.zeros((batch, T), dtype=torch.int64, device=dev)
+        self.pos_ids = torch.zeros((batch, T), dtype=torch.int64, device=dev)
+        self.accepted = torch.zeros(batch, dtype=torch.int32, device=dev)
+        self._steps = torch.zeros(batch, dtype=torch.int64, device=dev)
+        self._tokens = torch.zeros(batch, dtype=torch.int64, device=dev)
+        self._mask = torch.ones((batch, 1, T, self.max_len), dtype=torch.bool, device=dev)
+
+    def set_sampling(self, temperature=None, top_k=None, top_p=None) -> None:
+        """Greedy only: accepting a draft compares it with THE token of its row."""
+        if temperature is not None and bool((torch.as_tensor(temperature, dtype=torch.float32) > 0).any()):
+            raise ValueError("SpeculativeSession: speculative decoding is greedy only (no temperature)")
+
+    def _draft(self) -> None:
+        _ops.ngram_draft(self._hist_full, self.pos, self.tok, self.pos_ids, self.ngram)
+
+    def _pick(self, logits: torch.Tensor, rows: slice = slice(None)) -> None:
+        # prefill() and admit(): one row of logits per stream, the plain pick, then drafts for everyone
+        # (a stream whose state did not change gets the drafts it had, or others: they are hints)
+        r = rows
+        first = self.tok[r, :1].contiguous()
+        _ops.greedy_step_streams(logits, self._hist_next[r], self.pos[r], self.live[r], self.stop[r], self.limit[r],
+                                 first)
+        self.tok[r, :1] = first
+        self._draft()
+
+    def _step(self) -> None:
+        lo = self.model(input_ids=self.tok, past_key_values=self.cache, position_ids=self.pos_ids,
+                        attention_mask=self._mask, use_cache=True, _qz_verify_pos=self.pos).logits
+        _ops.verify_step_streams(lo.reshape(self.batch * self.T, -1), self._hist_next, self.pos, self.live, self.stop,
+                                 self.limit, self.tok, self.accepted)
+        self._tokens.add_(self.accepted)
+        self._steps.add_(self.accepted.ne(0))
+        self._draft()
+
+    def _step_state(self) -> list:
+        return super()._step_state() + [self.pos_ids, self.accepted, self._steps, self._tokens]
+
+    def stats(self) -> dict:
+        """Running totals per stream, read from the device now: "steps" the steps the stream was live
+        in, "tokens" the tokens those steps emitted (prefill's and admit's first tokens are not steps)."""
+        return {"steps": self._steps.cpu(), "tokens": self._tokens.cpu()}
+
+
+def _speculative_session(model, batch: int, max_len: int, prompt_lookup_num_tokens, max_matching_ngram_size,
+                         do_sample: bool, graph: bool, who: str) -> SpeculativeSession:
+    if do_sample:
+        raise ValueError(f"{who}: prompt_lookup_num_tokens verifies drafts against the greedy token; "
+                         "do_sample is not supported with it")
+    n = PROMPT_LOOKUP_NGRAM if max_matching_ngram_size is None else int(max_matching_ngram_size)
+    return SpeculativeSession(model, batch, max_len, draft_tokens=int(prompt_lookup_num_tokens), ngram=n, graph=graph)
+
+
+def _run_speculative(sess: SpeculativeSession, max_new_tokens: int) -> None:
+    """Step until no stream is live: at most max_new_tokens - 1 steps, a host look every few."""
+    for n in range(1, max_new_tokens):
+        sess.step()
+        if n % SPECULATIVE_CHECK_EVERY == 0 and not bool(sess.alive().any()):
+            break
+
+
+def _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attention_mask, graph,
+                          prompt_lookup_num_tokens, max_matching_ngram_size) -> torch.Tensor:
+    """generate()'s result from a SpeculativeSession: every stream runs to its EOS or to max_new_tokens,
+    then the rows are laid out as the plain loop leaves them -- S + n columns, n the first multiple of
+    STOP_CHECK_EVERY by which every stream had its EOS (max_new_tokens if there is none), each
+    stream's tokens after its EOS that EOS."""
+    if attention_mask is not None and not bool(attention_mask.bool().all()):
+        raise ValueError("generate: padded prompts are not supported (attention_mask holds a zero)")
+    B, S = input_ids.shape
+    sess = _speculative_session(model, B, S + max_new_tokens, prompt_lookup_num_tokens, max_matching_ngram_size,
+                                False, graph, "generate")
+    sess.prefill(input_ids, [S] * B, stop=eos_token_id, max_new_tokens=max_new_tokens)
+    _run_speculative(sess, max_new_tokens)
+    seqs = sess.sequences()
+    n = max_new_tokens
+    if eos_token_id is not None and all(int(s[-1]) == eos_token_id for s in seqs):
+        longest = max(s.numel() for s in seqs) - S
+        n = min(max_new_tokens, -(-longest // STOP_CHECK_EVERY) * STOP_CHECK_EVERY)
+    fill = 0 if eos_token_id is None else eos_token_id
+    out = torch.full((B, S + n), fill, dtype=torch.int64, device=sess.device)
+    for b, s in enumerate(seqs):
+        out[b, :s.numel()] = s
+    return out
+
+
 @torch.inference_mode()
 def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, do_sample: bool = False,
                     temperature: Union[float, Sequence[float]] = 1.0, top_k: Union[int, Sequence[int]] = 0,
                     top_p: Union[float, Sequence[float]] = 1.0, generator=None, eos_token_id: Optional[int] = None,
-                    graph: bool = True) -> list:
+                    graph: bool = True, prompt_lookup_num_tokens: Optional[int] = None,
+                    max_matching_ngram_size: Optional[int] = None) -> list:
     """generate() for prompts of different lengths: `prompts` are 1-D int64 tensors; returns one 1-D
     int64 tensor per prompt on the model's device, the prompt followed by up to max_new_tokens picked
     tokens of its own, ending with eos_token_id if the stream picked it.  A stream that stopped writes
     nothing more; the host looks at `live` every STOP_CHECK_EVERY steps and returns once none is.
-    One GPU and prepare_for_decode()'s layout; anything else raises."""
+    One GPU and prepare_for_decode()'s layout; anything else raises.
+    prompt_lookup_num_tokens (transformers' name): verify that many prompt-lookup drafts per stream
+    and step in a SpeculativeSession (suffixes of up to max_matching_ngram_size tokens, default 2) --
+    greedy only, the same tokens in fewer steps wherever the text repeats itself."""
     prompts = list(prompts)
     if not prompts or any((not isinstance(p, torch.Tensor)) or p.dim() != 1 or p.numel() < 1 for p in prompts):
         raise ValueError("generate_ragged: prompts must be a non-empty sequence of non-empty 1-D tensors")
@@ -461,7 +605,13 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
         raise ValueError("generate_ragged: max_new_tokens must be positive")
     lens = [p.numel() for p in prompts]
     B, Smax = len(prompts), max(lens)
-    sess = StreamSession(model, B, Smax + max_new_tokens, graph=graph)
+    if prompt_lookup_num_tokens is not None:
+        sess = _speculative_session(model, B, Smax + max_new_tokens, prompt_lookup_num_tokens,
+                                    max_matching_ngram_size, do_sample, graph, "generate_ragged")
+    elif max_matching_ngram_size is not None:
+        raise ValueError("generate_ragged: max_matching_ngram_size needs prompt_lookup_num_tokens")
+    else:
+        sess = StreamSession(model, B, Smax + max_new_tokens, graph=graph)
     if do_sample:
         sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
         sess.seed(generator)
@@ -469,6 +619,9 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     for b, p in enumerate(prompts):
         ids[b, :lens[b]] = p.to(sess.device)
     sess.prefill(ids, lens, stop=eos_token_id, max_new_tokens=max_new_tokens)
+    if isinstance(sess, SpeculativeSession):
+        _run_speculative(sess, max_new_tokens)
+        return sess.sequences()
     n = 1
     while n < max_new_tokens:
         sess.step()

@@ -294,9 +294,13 @@ def _fused_attention_forward(mod: nn.Module, orig):
 
     `_qz_stream_pos` (int64 [B] on the GPU, generation.StreamSession): every stream has its own
     position, so the layer runs layer_ops.decode_attention_streams -- or raises: the original
-    forward and the shared-position launch would both write every stream's k/v at one slot."""
+    forward and the shared-position launch would both write every stream's k/v at one slot.
+
+    `_qz_verify_pos` (int64 [B], generation.SpeculativeSession): hidden_states is [B, T, H], a window
+    of T >= 2 tokens per stream at positions pos[b] .. pos[b] + T - 1, position_embeddings [B, T, D];
+    the layer runs layer_ops.decode_attention_verify -- or raises, for the same reason."""
     from .layer_ops import (decode_attention, decode_attention_streams, decode_attention_streams_supported,
-                            decode_attention_supported)
+                            decode_attention_supported, decode_attention_verify, decode_attention_verify_supported)
 
     def stream_forward(hidden_states, position_embeddings, past_key_values, pos, residual, kwargs):
         layer = None
@@ -318,9 +322,34 @@ def _fused_attention_forward(mod: nn.Module, orig):
         out = decode_attention_streams(q, k, v, cos, sin, layer.keys, layer.values, pos, nq, mod.scaling)
         return _project(mod.o_proj, out, residual), None
 
+    def verify_forward(hidden_states, position_embeddings, past_key_values, pos, residual, kwargs):
+        layer = None
+        if (hidden_states.dim() == 3 and hidden_states.shape[1] >= 2 and position_embeddings is not None
+                and not kwargs.get("output_attentions", False) and not mod.training):
+            layer = _static_layer(past_key_values, getattr(mod, "layer_idx", None))
+        if layer is None or layer.keys.dim() != 4 or layer.keys.shape[-1] != mod.head_dim:
+            raise ValueError("_qz_verify_pos: a verify window needs at least two tokens per stream against an "
+                             "initialised StaticCache layer of this module's head_dim")
+        cos, sin = position_embeddings
+        nq = layer.keys.shape[1] * (mod.config.num_attention_heads // mod.config.num_key_value_heads)
+        if not decode_attention_verify_supported(hidden_states, cos, layer.keys, layer.values, pos, nq):
+            raise ValueError("_qz_verify_pos: decode_attention_verify does not take these shapes/dtypes/layout")
+        q = mod.q_proj(hidden_states)
+        k = mod.k_proj(hidden_states)
+        v = mod.v_proj(hidden_states)
+        if q.shape[-1] != nq * mod.head_dim or k.shape[-1] != layer.keys.shape[1] * mod.head_dim:
+            raise ValueError("_qz_verify_pos: the projections' widths differ from the cache's heads")
+        out = decode_attention_verify(q, k, v, cos, sin, layer.keys, layer.values, pos, nq, mod.scaling)
+        return _project(mod.o_proj, out, residual), None
+
     def forward(hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None,
-                _qz_residual=None, _qz_stream_pos=None, **kwargs):
+                _qz_residual=None, _qz_stream_pos=None, _qz_verify_pos=None, **kwargs):
         # _qz_residual (the residual-fused decoder layer): return residual + attention output
+        if _qz_verify_pos is not None:   # taken out of kwargs, like _qz_stream_pos below
+            if _qz_stream_pos is not None:
+                raise ValueError("_qz_verify_pos and _qz_stream_pos exclude each other")
+            return verify_forward(hidden_states, position_embeddings, past_key_values, _qz_verify_pos, _qz_residual,
+                                  kwargs)
         if _qz_stream_pos is not None:   # taken out of kwargs: the original forward never sees it
             return stream_forward(hidden_states, position_embeddings, past_key_values, _qz_stream_pos, _qz_residual,
                                   kwargs)

@@ -13,7 +13,10 @@ projections (csrc/layer_ops.hip, C-ABI include/quantizations.h):
 ``greedy_step`` / ``sample_step`` are a decode loop's token pick with its feedback (csrc/sample.hip for the
 sampled one, which alone has a composed torch route: fp32 or CPU logits).  ``decode_attention_streams``,
 ``greedy_step_streams`` and ``sample_step_streams`` are their forms with a position per stream
-(generation.StreamSession); both streams picks have a composed torch route.
+(generation.StreamSession); both streams picks have a composed torch route.  ``decode_attention_verify``,
+``verify_step_streams`` and ``ngram_draft`` are the three launches of a speculative greedy step
+(generation.SpeculativeSession): a window of T tokens per stream, the pick that accepts the longest
+matching prefix of its drafts, and the prompt-lookup drafter; the last two have a composed / host route.
 
 None of them is in the reference (it leaves them to transformers).  They exist
 because at batch-1 decode the eager torch forms cost ~8, ~10 and 2 dependent
@@ -254,6 +257,72 @@ def decode_attention_streams(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
         value_cache.data_ptr(), pos.data_ptr(), out.data_ptr(), num_heads * D,
         work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)),
         "qz_decode_attention_streams")
+    return out
+
+
+def decode_attention_verify_supported(q: torch.Tensor, cos: torch.Tensor, key_cache: torch.Tensor,
+                                      value_cache: torch.Tensor, pos, num_heads: int) -> bool:
+    """What qz_decode_attention_verify takes: T >= 2 new tokens per stream (q, or the layer input:
+    [B, T, *]), 16-bit activations, decode_attention_streams_supported's caches and pos [B], and
+    cos/sin [B, T, D] whose B T rows lie at one stride.  Metadata only: nothing is launched or
+    allocated."""
+    if _needs_grad(q) or not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype in (torch.float16, torch.bfloat16)
+                              and q.dim() == 3 and q.shape[1] >= 2):
+        return False
+    if key_cache.dim() != 4 or value_cache.shape != key_cache.shape:
+        return False
+    B, Hkv, L, D = key_cache.shape
+    T = q.shape[1]
+    if (D not in (64, 128) or Hkv == 0 or num_heads % Hkv or num_heads // Hkv > 8 or q.shape[0] != B or L == 0
+            or B * T > 65535):
+        return False
+    for t in (key_cache, value_cache):
+        if t.dtype != q.dtype or t.device != q.device or not t.is_contiguous() or t.data_ptr() % 16:
+            return False
+    if not (cos.dim() == 3 and tuple(cos.shape) == (B, T, D) and cos.dtype == q.dtype and cos.device == q.device
+            and cos.stride(-1) == 1 and (B == 1 or cos.stride(0) == T * cos.stride(1))):
+        return False
+    return (isinstance(pos, torch.Tensor) and pos.dtype == torch.int64 and pos.dim() == 1
+            and pos.shape[0] == B and pos.device == q.device and pos.is_contiguous())
+
+
+def decode_attention_verify(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                            key_cache: torch.Tensor, value_cache: torch.Tensor, pos: torch.Tensor, num_heads: int,
+                            scale: float) -> torch.Tensor:
+    """decode_attention_streams for a window of T tokens per stream (qz_decode_attention_verify): q
+    [B, T, Hq*D], k/v [B, T, Hkv*D], cos/sin [B, T, D], pos int64 [B].  Token (b, i) sits at position
+    pos[b] + i: its k/v go to that slot of cache row b and it sees keys 0..pos[b] + i, the window's
+    earlier tokens included.  Outputs and caches carry the bits of T successive
+    decode_attention_streams calls on stream b alone, so a token's result does not depend on its row.
+    A row past the cache end is NaN and writes nothing; pos[b] < 0 makes stream b's T rows NaN; pos
+    is left as it is.  Returns [B, T, Hq*D]."""
+    if not decode_attention_verify_supported(q, cos, key_cache, value_cache, pos, num_heads):
+        raise ValueError("decode_attention_verify: unsupported shapes/dtypes/layout")
+    B, Hkv, L, D = key_cache.shape
+    T, G = q.shape[1], num_heads // Hkv
+    if q.shape[2] != num_heads * D:
+        raise ValueError("decode_attention_verify: q width differs from num_heads * head_dim")
+    if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
+        raise ValueError("decode_attention_verify: sin must match cos")
+    if k.shape[:2] != q.shape[:2] or v.shape[:2] != q.shape[:2]:
+        raise ValueError("decode_attention_verify: k/v must hold q's [B, T] rows")
+    R = B * T
+    q2, k2, v2 = (t.reshape(R, -1) for t in (q, k, v))
+    k2 = k2 if k2.stride(-1) == 1 else k2.contiguous()
+    q2 = q2 if q2.stride(-1) == 1 else q2.contiguous()
+    if v2.stride(-1) != 1 or v2.stride(0) % 2 or v2.data_ptr() % 4:
+        v2 = v2.contiguous()
+    if k2.shape[1] != Hkv * D or v2.shape[1] != Hkv * D:
+        raise ValueError("decode_attention_verify: k/v width differs from the cache's heads")
+    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
+    nsplit = -(-L // ATTN_CHUNK)
+    work = torch.empty(R * Hkv * nsplit * G * (D + 2), dtype=torch.float32, device=q.device) if nsplit > 1 else None
+    _lib.check(_lib.lib.qz_decode_attention_verify(
+        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, L, q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0),
+        v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cos.stride(1), key_cache.data_ptr(),
+        value_cache.data_ptr(), pos.data_ptr(), out.data_ptr(), num_heads * D,
+        work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)),
+        "qz_decode_attention_verify")
     return out
 
 
@@ -532,3 +601,127 @@ def sample_step_streams(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Ten
         top_k.data_ptr(), top_p.data_ptr(), uniform.data_ptr(), uniform.shape[1], hist.data_ptr(), hist.shape[1],
         hist.shape[1], pos.data_ptr(), live.data_ptr(), stop.data_ptr(), limit.data_ptr(), tok.data_ptr(),
         work.data_ptr(), _lib.stream_of(logits)), "qz_sample_step_streams")
+
+
+VERIFY_MAX_T = 16   # kVerifyMaxT (csrc/layer_ops.hip): rows per stream of verify_step_streams / ngram_draft
+NGRAM_MAX = 4       # the longest suffix ngram_draft looks up
+
+
+def _check_verify(name, logits, hist, pos, live, stop, limit, tok, accepted):
+    if logits.dim() != 2 or logits.stride(-1) != 1:
+        raise ValueError(f"{name}: logits must be [B*T, V] with unit element stride")
+    for t, dt, what in ((hist, torch.int64, "hist"), (pos, torch.int64, "pos"), (tok, torch.int64, "tok"),
+                        (live, torch.int32, "live"), (stop, torch.int64, "stop"), (limit, torch.int64, "limit"),
+                        (accepted, torch.int32, "accepted")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != logits.device or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be contiguous {dt} on the logits' device")
+    if tok.dim() != 2 or not 1 <= tok.shape[1] <= VERIFY_MAX_T:
+        raise ValueError(f"{name}: tok must be [B, T] with T <= {VERIFY_MAX_T}")
+    B, T = tok.shape
+    if logits.shape[0] != B * T or hist.dim() != 2 or hist.shape[0] != B:
+        raise ValueError(f"{name}: logits [B*T, V], hist [B, H]")
+    for t, what in ((pos, "pos"), (live, "live"), (stop, "stop"), (limit, "limit"), (accepted, "accepted")):
+        if t.shape != (B,):
+            raise ValueError(f"{name}: {what} must be [B]")
+
+
+def _verify_step_streams_composed(logits, hist, pos, live, stop, limit, tok, accepted) -> None:
+    """qz_verify_step_streams' rules in torch ops (no host read): T masked rounds of _feedback_streams."""
+    B, T = tok.shape
+    H = hist.shape[1]
+    g = logits.argmax(-1).view(B, T)
+    going = live != 0
+    p, lv, last = pos.clone(), live.clone(), tok[:, 0].clone()
+    n = torch.zeros_like(accepted)
+    for i in range(T):
+        gi = g[:, i]
+        if H:
+            col = p.clamp(0, H - 1)[:, None]
+            inside = going & (p >= 0) & (p < H)
+            hist.scatter_(1, col, torch.where(inside, gi, hist.gather(1, col)[:, 0])[:, None])
+        p = torch.where(going, p + 1, p)
+        n = n + going.to(n.dtype)
+        last = torch.where(going, gi, last)
+        ended = going & ((gi == stop) | (p >= limit))
+        lv = torch.where(ended, torch.zeros_like(lv), lv)
+        if i + 1 < T:
+            going = going & ~ended & (tok[:, i + 1] == gi)
+    pos.copy_(p)
+    live.copy_(lv)
+    tok[:, 0] = last
+    accepted.copy_(n)
+
+
+def verify_step_streams(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, live: torch.Tensor,
+                        stop: torch.Tensor, limit: torch.Tensor, tok: torch.Tensor, accepted: torch.Tensor, *,
+                        composed: bool = False) -> None:
+    """The greedy pick that accepts drafts (qz_verify_step_streams).  tok int64 [B, T]: column 0 the
+    token that was fed, columns 1.. the drafts; logits [B*T, V], row b*T + i the model's output after
+    tok[b, :i + 1]; g_i its greedy_step pick.  A live stream does what successive
+    greedy_step_streams calls would: for i = 0, 1, ...: hist[b, pos[b]] = g_i, pos[b] += 1; it leaves
+    (live[b] = 0) and ends on its stop token or at its limit; it ends after row T - 1 or when draft
+    tok[b, i + 1] is not g_i.  tok[b, 0] becomes the last token emitted and accepted[b] (int32 [B]) the
+    number emitted; a stream that is not live has accepted[b] = 0 and nothing else written.  An
+    emitted row i has pos[b] + i + 1 <= limit[b], so with limit[b] <= L - 1 no row past the cache of
+    decode_attention_verify is ever emitted.  CPU logits, or composed=True, take the same rules in
+    torch ops."""
+    _check_verify("verify_step_streams", logits, hist, pos, live, stop, limit, tok, accepted)
+    B, T = tok.shape
+    V = logits.shape[1]
+    if composed or not logits.is_cuda:
+        if B and V:
+            _verify_step_streams_composed(logits, hist, pos, live, stop, limit, tok, accepted)
+        return
+    work = torch.empty(_lib.lib.qz_greedy_step_work_bytes(B * T, V), dtype=torch.uint8, device=logits.device)
+    _lib.check(_lib.lib.qz_verify_step_streams(
+        logits.data_ptr(), _lib.dtype_code(logits.dtype), B, T, V, logits.stride(0), hist.data_ptr(), hist.shape[1],
+        hist.shape[1], pos.data_ptr(), live.data_ptr(), stop.data_ptr(), limit.data_ptr(), tok.data_ptr(),
+        accepted.data_ptr(), work.data_ptr(), _lib.stream_of(logits)), "qz_verify_step_streams")
+
+
+def ngram_draft_reference(seq, tok0: int, p: int, T: int, ngram_max: int) -> list:
+    """The drafter's rule on host integers: seq[0..p] is the stream's history (seq[p] the newest
+    token), the result its T - 1 drafts."""
+    if 0 <= p < len(seq):
+        for n in range(min(ngram_max, p), 0, -1):
+            tail = list(seq[p - n + 1:p + 1])
+            for m in range(p - n, -1, -1):
+                if list(seq[m:m + n]) == tail:
+                    e = list(seq[:p + 1])
+                    for i in range(T - 1):
+                        e.append(e[m + n + i])
+                    return e[p + 1:]
+    return [tok0] * (T - 1)
+
+
+def ngram_draft(hist: torch.Tensor, pos: torch.Tensor, tok: torch.Tensor, pos_ids: torch.Tensor,
+                ngram_max: int = 3, *, composed: bool = False) -> None:
+    """The prompt-lookup drafter (qz_ngram_draft), one workgroup per stream: hist int64 [B, H] is the
+    sequence itself (hist[b, pos[b]] is tok[b, 0], the newest token), tok int64 [B, T], pos_ids int64
+    [B, T].  For n = ngram_max .. 1 with n <= pos[b]: the latest earlier copy of the last n tokens
+    (largest start m with m + n <= pos[b]); the first n that has one wins and the drafts
+    tok[b, 1:] are what followed it, running on into the drafts themselves where the copy ends at the
+    newest token.  No match: every draft is tok[b, 0].  Also pos_ids[b, i] = pos[b] + i.  Drafts are
+    hints: no result may depend on them.  CPU tensors, or composed=True, run ngram_draft_reference on
+    the host."""
+    for t, what in ((hist, "hist"), (pos, "pos"), (tok, "tok"), (pos_ids, "pos_ids")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.device != hist.device or not t.is_contiguous():
+            raise ValueError(f"ngram_draft: {what} must be contiguous int64 on one device")
+    if tok.dim() != 2 or not 1 <= tok.shape[1] <= VERIFY_MAX_T or pos_ids.shape != tok.shape:
+        raise ValueError(f"ngram_draft: tok and pos_ids must be [B, T] with T <= {VERIFY_MAX_T}")
+    B, T = tok.shape
+    if hist.dim() != 2 or hist.shape[0] != B or pos.shape != (B,):
+        raise ValueError("ngram_draft: hist [B, H], pos [B]")
+    if not 1 <= int(ngram_max) <= NGRAM_MAX:
+        raise ValueError(f"ngram_draft: ngram_max must be in 1..{NGRAM_MAX}")
+    if composed or not hist.is_cuda:
+        h, ps, tk = hist.cpu().tolist(), pos.cpu().tolist(), tok.cpu()
+        for b in range(B):
+            tk[b, 1:] = torch.tensor(ngram_draft_reference(h[b], int(tk[b, 0]), ps[b], T, int(ngram_max)),
+                                     dtype=torch.int64)
+        tok.copy_(tk)
+        pos_ids.copy_(pos[:, None] + torch.arange(T, device=pos.device)[None, :])
+        return
+    _lib.check(_lib.lib.qz_ngram_draft(B, T, int(ngram_max), hist.data_ptr(), hist.shape[1], hist.shape[1],
+                                       pos.data_ptr(), tok.data_ptr(), pos_ids.data_ptr(), _lib.stream_of(hist)),
+               "qz_ngram_draft")

@@ -442,6 +442,17 @@ int qz_sample_step_streams(const void *logits, int dtype, int B, long long V, lo
  *   A stream that is not live has accepted[b] = 0 and nothing else written.  Emitted row i has
  *   pos + i + 1 <= limit[b]: with limit[b] <= L - 1 no row past the cache is ever emitted.
  *   T <= 16, B*T <= 65535 (QZ_ERR_SHAPE); F16/BF16/F32; work: qz_greedy_step_work_bytes(B*T, V).
+ * qz_verify_sample_step_streams: the sampled pick that accepts drafts (six launches for any T,
+ *   csrc/sample.hip).  The same operands and the same loop with g_i := s_i, the token
+ *   qz_sample_step_streams picks for row b*T + i alone with stream b's temperature[b], top_k[b] and
+ *   top_p[b] at position pos[b] + i, i.e. u = uniform[b, clamp(pos[b] + i, 0, hist_len - 1)]
+ *   (pos[b] as it is before the call; greedy rows, NaN ranking, ties and the last-kept-index fallback
+ *   as there).  s_i is a function of the row and of u alone, so the tokens emitted are those of
+ *   successive qz_sample_step_streams calls over the same uniform table whatever the drafts were:
+ *   draft i + 1 is accepted with probability p(draft), and a rejected one leaves a token distributed
+ *   as p given "not the draft".  T <= 16, B*T <= 65535 (QZ_ERR_SHAPE); F16/BF16 (QZ_ERR_DTYPE);
+ *   work: qz_verify_sample_step_work_bytes(B, T, V) bytes, 16-B aligned, any content; B, T or V of 0
+ *   is QZ_OK with nothing launched.
  * qz_ngram_draft: the prompt-lookup drafter, one workgroup per stream.  s = hist[b, 0..p], p = pos[b]
  *   (s[p] is tok[b, 0]).  For n = ngram_max .. 1 with n <= p: the largest m with m + n <= p and
  *   s[m .. m+n-1] == s[p-n+1 .. p]; the first n that has one wins.  With e = s followed by the
@@ -452,6 +463,12 @@ int qz_verify_step_streams(const void *logits, int dtype, int B, int T, long lon
                            long long hist_row, long long hist_len, long long *pos, int *live,
                            const long long *stop, const long long *limit, long long *tok, int *accepted,
                            void *work, void *stream);
+long long qz_verify_sample_step_work_bytes(int B, int T, long long V);
+int qz_verify_sample_step_streams(const void *logits, int dtype, int B, int T, long long V, long long row,
+                                  const float *temperature, const int *top_k, const float *top_p,
+                                  const float *uniform, long long uniform_row, long long *hist, long long hist_row,
+                                  long long hist_len, long long *pos, int *live, const long long *stop,
+                                  const long long *limit, long long *tok, int *accepted, void *work, void *stream);
 int qz_ngram_draft(int B, int T, int ngram_max, const long long *hist, long long hist_row, long long hist_len,
                    const long long *pos, long long *tok, long long *pos_ids, void *stream);
 /* qz_gemv_dense: the model's fp16/bf16 lm_head for one decode token (transformers keeps it

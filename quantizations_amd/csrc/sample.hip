@@ -25,6 +25,13 @@
 // qz_sample_step_streams launches the same five kernels with a position per stream (pos_stride 1)
 // and the live / stop / limit words: a stream that is not live is still scanned (its row costs what
 // it cost before) but k_sample_final writes nothing of it.
+//
+// qz_verify_sample_step_streams runs the five over the B T rows of a verify window: the rows-per-
+// stream count is a run-time operand (1 above), row r has its own bins, partials and header, reads
+// stream r / T's temperature, top-k, top-p and uniform row and is drawn at position pos[r / T] + r % T.
+// k_sample_final then leaves the row's token in the header instead of writing the feedback, and a
+// sixth launch, k_verify_sample_accept (B workgroups x 64), emits each stream's tokens for as long as
+// the next draft is the token just drawn -- six launches for any T.
 #include <limits.h>
 
 #include "common.h"
@@ -43,7 +50,9 @@ struct SampleHdr {   // per stream, written by k_sample_scan
   float smax, u, T;
   int thr_key;       // sampled rows: keep key >= thr_key
   int greedy;
-  int pad[7];
+  int pad0;
+  long long tok;     // rows of a verify window: the row's token, left by k_sample_final
+  int pad[4];
 };
 static_assert(sizeof(SampleHdr) == 64, "header is 64 bytes");
 
@@ -178,14 +187,16 @@ __global__ __launch_bounds__(256) void k_sample_clear(void *work, int nb, long l
 
 template <int DT>
 __global__ __launch_bounds__(256) void k_sample_hist(const void *logits, long long row, long long V, int nb,
-                                                     const float *temperature, void *work, long long sbytes, bool vec) {
+                                                     const float *temperature, int T, void *work,
+                                                     long long sbytes, bool vec) {
   __shared__ float s_v[4];
   __shared__ long long s_i[4];
   const int tid = threadIdx.x, b = blockIdx.y;
   const SampleWork w = work_of(work, b, nb, sbytes);
   const unsigned char *lr = reinterpret_cast<const unsigned char *>(logits) + (size_t)b * row * 2;
   const long long i0 = (long long)blockIdx.x * kSampleChunk + tid * 8;
-  const bool sampled = temperature[b] > 0.0f;
+  // T rows per stream: row b belongs to stream b / T (no division on the one-row entry points' path)
+  const bool sampled = temperature[T == 1 ? b : b / T] > 0.0f;
   uint32_t h[8];
   const int n = load8(lr, i0, V, vec, h);
   float best = -__builtin_inff();
@@ -208,7 +219,8 @@ __global__ __launch_bounds__(kScanThreads) void k_sample_scan(long long V, int n
                                                               const int *top_k, const float *top_p,
                                                               const float *uniform, long long uniform_row,
                                                               long long hist_len, const long long *pos,
-                                                              long long pos_stride, void *work, long long sbytes) {
+                                                              long long pos_stride, int rows, void *work,
+                                                              long long sbytes) {
   __shared__ float s_v[16];
   __shared__ long long s_i[16];
   __shared__ unsigned s_c[256];
@@ -220,7 +232,9 @@ __global__ __launch_bounds__(kScanThreads) void k_sample_scan(long long V, int n
   __shared__ unsigned s_dkt, s_thr;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
   const SampleWork w = work_of(work, b, nb, sbytes);
-  const float T = temperature[b];
+  // `rows` logits rows per stream (1 but for a verify window): row b is row b % rows of stream sb
+  const int sb = rows == 1 ? b : b / rows;
+  const float T = temperature[sb];
 
   float best = -__builtin_inff();
   long long bi = V;
@@ -231,11 +245,11 @@ __global__ __launch_bounds__(kScanThreads) void k_sample_scan(long long V, int n
   }
   greedy_reduce<16>(best, bi, V, s_v, s_i);
   if (tid == 0) {
-    const long long p = pos[(size_t)b * pos_stride];
+    const long long p = pos[(size_t)sb * pos_stride] + (b - sb * rows);
     float u = 0.0f;
     if (hist_len > 0) {
       const long long q = p < 0 ? 0 : (p < hist_len ? p : hist_len - 1);
-      u = uniform[(size_t)b * uniform_row + q];
+      u = uniform[(size_t)sb * uniform_row + q];
     }
     const bool finite = bi != V && best == best && fabsf(best) != __builtin_inff();
     const int g = !(T > 0.0f) || !finite;
@@ -308,7 +322,7 @@ __global__ __launch_bounds__(kScanThreads) void k_sample_scan(long long V, int n
   __syncthreads();
 
   // top-k: the bin whose inclusive count reaches k first; Z = the weight down to it
-  const int k = top_k[b];
+  const int k = top_k[sb];
   if (k >= 1 && (long long)k < V) {
 #pragma unroll
     for (int j = 0; j < kScanRounds; ++j) {
@@ -334,7 +348,7 @@ __global__ __launch_bounds__(kScanThreads) void k_sample_scan(long long V, int n
 
   // top-p: keep a bin iff the weight strictly above it is below P * Z; the maximal bin always stays
   const unsigned dkt = s_dkt;
-  const float P = top_p[b];
+  const float P = top_p[sb];
   const bool pon = P < 1.0f;
   const float PZ = __fmul_rn(P, s_Z);
   unsigned cand = 0;
@@ -405,8 +419,8 @@ template <int DT>
 __global__ __launch_bounds__(256) void k_sample_final(const void *logits, long long row, long long V, int nb,
                                                       long long *hist, long long hist_row, long long hist_len,
                                                       long long *pos, int *live, const long long *stop,
-                                                      const long long *limit, long long *tok, void *work,
-                                                      long long sbytes, bool vec) {
+                                                      const long long *limit, long long *tok, bool defer,
+                                                      void *work, long long sbytes, bool vec) {
   __shared__ float s4[4];
   __shared__ int s_chunk, s_lastc, s_loc;
   __shared__ float s_base;
@@ -477,6 +491,10 @@ __global__ __launch_bounds__(256) void k_sample_final(const void *logits, long l
       if (fin >= 0) token = (long long)chunk * kSampleChunk + fin;
     }
   }
+  if (defer) {   // a row of a verify window: k_verify_sample_accept decides what becomes of its token
+    if (tid == 0) w.hdr->tok = token;
+    return;
+  }
   if (tid == 0 && (!live || live[b] != 0)) {
     // a position past the history writes nothing there: the token and the position still advance
     if (p >= 0 && p < hist_len) hist[(size_t)b * hist_row + p] = token;
@@ -490,6 +508,38 @@ __global__ __launch_bounds__(256) void k_sample_final(const void *logits, long l
   }
 }
 
+// The accept loop of qz_verify_sample_step_streams, one workgroup (one wave) per stream: lane i
+// fetches the token k_sample_final left in row b T + i's header and the draft tok[b, i], then
+// thread 0 does what thread 0 of k_verify_final does with the greedy picks.
+constexpr int kVerifySampleMaxT = 16;
+__global__ __launch_bounds__(64) void k_verify_sample_accept(int T, int nb, long long *hist, long long hist_row,
+                                                             long long hist_len, long long *pos, long long *tok,
+                                                             int *live, const long long *stop, const long long *limit,
+                                                             int *accepted, void *work, long long sbytes) {
+  __shared__ long long s_g[kVerifySampleMaxT], s_d[kVerifySampleMaxT];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  if (tid < T) {
+    s_g[tid] = work_of(work, b * T + tid, nb, sbytes).hdr->tok;
+    s_d[tid] = tok[(size_t)b * T + tid];
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  if (live[b] == 0) { accepted[b] = 0; return; }
+  long long p = pos[b], g = 0;
+  int n = 0;
+  for (int i = 0; i < T; ++i) {
+    g = s_g[i];
+    if (p >= 0 && p < hist_len) hist[(size_t)b * hist_row + p] = g;
+    p += 1;
+    n += 1;
+    if (g == stop[b] || p >= limit[b]) { live[b] = 0; break; }
+    if (i == T - 1 || s_d[i + 1] != g) break;
+  }
+  tok[(size_t)b * T] = g;
+  pos[b] = p;
+  accepted[b] = n;
+}
+
 }  // namespace
 }  // namespace qz
 
@@ -500,30 +550,38 @@ extern "C" long long qz_sample_step_work_bytes(int B, long long V) {
   return (long long)B * stream_bytes((V + kSampleChunk - 1) / kSampleChunk);
 }
 
-static int sample_step_launch(const void *logits, int dtype, int B, long long V, long long row,
+// The five launches over R = B * T logits rows, T rows per stream (T = 1 but for a verify window:
+// row r is row r % T of stream r / T, drawn at position pos[r / T] + r % T).  With `accepted` the
+// rows' tokens stay in their headers and k_verify_sample_accept writes the feedback.
+static int sample_step_launch(const void *logits, int dtype, int B, int T, long long V, long long row,
                               const float *temperature, const int *top_k, const float *top_p, const float *uniform,
                               long long uniform_row, long long *hist, long long hist_row, long long hist_len,
                               long long *pos, long long pos_stride, int *live, const long long *stop,
-                              const long long *limit, long long *tok, void *work, void *stream) {
+                              const long long *limit, long long *tok, int *accepted, void *work, void *stream) {
   if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) return QZ_ERR_DTYPE;
   const long long nbl = (V + kSampleChunk - 1) / kSampleChunk;
-  if (nbl > 0x7FFFFFFFLL || B > 65535) return QZ_ERR_SHAPE;
-  const int nb = (int)nbl;
+  if (nbl > 0x7FFFFFFFLL || (long long)B * T > 65535) return QZ_ERR_SHAPE;
+  const int nb = (int)nbl, R = B * T;
   const long long sbytes = stream_bytes(nb);
   hipStream_t s = (hipStream_t)stream;
   const bool vec = V % 8 == 0 && row % 8 == 0 && (uintptr_t)logits % 16 == 0;
-  const dim3 g((unsigned)nb, (unsigned)B);
-  hipLaunchKernelGGL(k_sample_clear, dim3(kBins / 4 / 256, (unsigned)B), dim3(256), 0, s, work, nb, sbytes);
+  const bool defer = accepted != nullptr;
+  const dim3 g((unsigned)nb, (unsigned)R);
+  hipLaunchKernelGGL(k_sample_clear, dim3(kBins / 4 / 256, (unsigned)R), dim3(256), 0, s, work, nb, sbytes);
 #define QZ_SAMPLE_LAUNCH(DT)                                                                                        \
-  hipLaunchKernelGGL((k_sample_hist<DT>), g, dim3(256), 0, s, logits, row, V, nb, temperature, work, sbytes, vec);  \
-  hipLaunchKernelGGL((k_sample_scan<DT>), dim3((unsigned)B), dim3(kScanThreads), 0, s, V, nb, temperature, top_k,   \
-                     top_p, uniform, uniform_row, hist_len, pos, pos_stride, work, sbytes);                         \
+  hipLaunchKernelGGL((k_sample_hist<DT>), g, dim3(256), 0, s, logits, row, V, nb, temperature, T, work, sbytes,     \
+                     vec);                                                                                          \
+  hipLaunchKernelGGL((k_sample_scan<DT>), dim3((unsigned)R), dim3(kScanThreads), 0, s, V, nb, temperature, top_k,   \
+                     top_p, uniform, uniform_row, hist_len, pos, pos_stride, T, work, sbytes);                      \
   hipLaunchKernelGGL((k_sample_chunk<DT>), g, dim3(256), 0, s, logits, row, V, nb, work, sbytes, vec);              \
-  hipLaunchKernelGGL((k_sample_final<DT>), dim3((unsigned)B), dim3(256), 0, s, logits, row, V, nb, hist, hist_row,  \
-                     hist_len, pos, live, stop, limit, tok, work, sbytes, vec)
+  hipLaunchKernelGGL((k_sample_final<DT>), dim3((unsigned)R), dim3(256), 0, s, logits, row, V, nb, hist, hist_row,  \
+                     hist_len, pos, live, stop, limit, tok, defer, work, sbytes, vec)
   if (dtype == QZ_DT_F16) { QZ_SAMPLE_LAUNCH(QZ_DT_F16); }
   else { QZ_SAMPLE_LAUNCH(QZ_DT_BF16); }
 #undef QZ_SAMPLE_LAUNCH
+  if (defer)
+    hipLaunchKernelGGL(k_verify_sample_accept, dim3((unsigned)B), dim3(64), 0, s, T, nb, hist, hist_row, hist_len, pos,
+                       tok, live, stop, limit, accepted, work, sbytes);
   return (int)hipGetLastError();
 }
 
@@ -536,8 +594,8 @@ extern "C" int qz_sample_step(const void *logits, int dtype, int B, long long V,
   if (!logits || !temperature || !top_k || !top_p || !uniform || !hist || !pos || !tok || !work || row < V ||
       (uintptr_t)work % 16 != 0 || (B > 1 && (hist_row < hist_len || uniform_row < hist_len)))
     return QZ_ERR_ARG;
-  return sample_step_launch(logits, dtype, B, V, row, temperature, top_k, top_p, uniform, uniform_row, hist, hist_row,
-                            hist_len, pos, 0, nullptr, nullptr, nullptr, tok, work, stream);
+  return sample_step_launch(logits, dtype, B, 1, V, row, temperature, top_k, top_p, uniform, uniform_row, hist,
+                            hist_row, hist_len, pos, 0, nullptr, nullptr, nullptr, tok, nullptr, work, stream);
 }
 
 extern "C" int qz_sample_step_streams(const void *logits, int dtype, int B, long long V, long long row,
@@ -552,6 +610,28 @@ extern "C" int qz_sample_step_streams(const void *logits, int dtype, int B, long
       !work || row < V || (uintptr_t)work % 16 != 0 ||
       (B > 1 && (hist_row < hist_len || uniform_row < hist_len)))
     return QZ_ERR_ARG;
-  return sample_step_launch(logits, dtype, B, V, row, temperature, top_k, top_p, uniform, uniform_row, hist, hist_row,
-                            hist_len, pos, 1, live, stop, limit, tok, work, stream);
+  return sample_step_launch(logits, dtype, B, 1, V, row, temperature, top_k, top_p, uniform, uniform_row, hist,
+                            hist_row, hist_len, pos, 1, live, stop, limit, tok, nullptr, work, stream);
+}
+
+extern "C" long long qz_verify_sample_step_work_bytes(int B, int T, long long V) {
+  if (B <= 0 || T <= 0 || V <= 0) return 0;
+  return (long long)B * T * stream_bytes((V + kSampleChunk - 1) / kSampleChunk);
+}
+
+extern "C" int qz_verify_sample_step_streams(const void *logits, int dtype, int B, int T, long long V, long long row,
+                                             const float *temperature, const int *top_k, const float *top_p,
+                                             const float *uniform, long long uniform_row, long long *hist,
+                                             long long hist_row, long long hist_len, long long *pos, int *live,
+                                             const long long *stop, const long long *limit, long long *tok,
+                                             int *accepted, void *work, void *stream) {
+  if (B < 0 || T < 0 || V < 0 || row < 0 || uniform_row < 0 || hist_row < 0 || hist_len < 0) return QZ_ERR_ARG;
+  if (B == 0 || T == 0 || V == 0) return QZ_OK;
+  if (!logits || !temperature || !top_k || !top_p || !uniform || !hist || !pos || !live || !stop || !limit || !tok ||
+      !accepted || !work || row < V || (uintptr_t)work % 16 != 0 ||
+      (B > 1 && (hist_row < hist_len || uniform_row < hist_len)))
+    return QZ_ERR_ARG;
+  if (T > kVerifySampleMaxT || (long long)B * T > 65535) return QZ_ERR_SHAPE;
+  return sample_step_launch(logits, dtype, B, T, V, row, temperature, top_k, top_p, uniform, uniform_row, hist,
+                            hist_row, hist_len, pos, 1, live, stop, limit, tok, accepted, work, stream);
 }

@@ -7,8 +7,9 @@ a replay follows set_sampling() -- or layer_ops.greedy_step when every stream is
 DecodeSession / generate() take equal-length prompts and move every stream together; StreamSession
 / generate_ragged() keep a position per stream on the device (prompts of different lengths, a
 finished stream's row handed to the next prompt without recapturing).  SpeculativeSession /
-prompt_lookup_num_tokens= verify prompt-lookup drafts: several greedy tokens per stream and step, the
-same tokens in fewer reads of the weights.  One GPU only; no penalties, no beams.
+prompt_lookup_num_tokens= verify prompt-lookup drafts: several tokens per stream and step, the
+same tokens in fewer reads of the weights -- greedy, or with sample=True / prompt_lookup_sampling=True
+the tokens each position's uniform number draws.  One GPU only; no penalties, no beams.
 """
 from __future__ import annotations
 
@@ -209,7 +210,7 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
              top_p: Union[float, Sequence[float]] = 1.0, generator=None, eos_token_id: Optional[int] = None,
              attention_mask: Optional[torch.Tensor] = None, graph: bool = True,
              prompt_lookup_num_tokens: Optional[int] = None,
-             max_matching_ngram_size: Optional[int] = None) -> torch.Tensor:
+             max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False) -> torch.Tensor:
     """input_ids [B, S] (equal-length prompts) followed by up to max_new_tokens picked tokens per
     stream: greedy, or with do_sample temperature / top_k / top_p (scalars or one per stream; a
     temperature <= 0 keeps that stream greedy) drawn from `generator` (a torch.Generator or a seed).
@@ -218,21 +219,24 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
     [B, S + new] on the model's device.
     prompt_lookup_num_tokens (transformers' name): verify that many prompt-lookup drafts per stream
     and step in a SpeculativeSession (suffixes of up to max_matching_ngram_size tokens, default 2).
-    Greedy only; it needs prepare_for_decode()'s layout on one GPU; the result has the shape and the
-    EOS fill the plain call defines."""
+    Greedy unless prompt_lookup_sampling=True, which with do_sample accepts a draft when it is the token
+    the row's uniform number draws (SpeculativeSession(sample=True): the tokens of the one-token sampler
+    over the same numbers, whatever the drafts).  It needs prepare_for_decode()'s layout on one GPU; the
+    result has the shape and the EOS fill the plain call defines."""
     if input_ids.dim() != 2:
         raise ValueError("generate: input_ids must be [B, S]")
     B, S = input_ids.shape
     if prompt_lookup_num_tokens is None and max_matching_ngram_size is not None:
         raise ValueError("generate: max_matching_ngram_size needs prompt_lookup_num_tokens")
-    if prompt_lookup_num_tokens is not None and do_sample:
+    if prompt_lookup_num_tokens is not None and do_sample and not prompt_lookup_sampling:
         raise ValueError("generate: prompt_lookup_num_tokens verifies drafts against the greedy token; "
-                         "do_sample is not supported with it")
+                         "do_sample is not supported with it unless prompt_lookup_sampling=True")
     if max_new_tokens < 1:
         return input_ids.clone()
     if prompt_lookup_num_tokens is not None:
+        sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator) if do_sample else None
         return _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attention_mask, graph,
-                                     prompt_lookup_num_tokens, max_matching_ngram_size)
+                                     prompt_lookup_num_tokens, max_matching_ngram_size, sampling)
     sess = DecodeSession(model, B, S + max_new_tokens, graph=graph)
     if do_sample:
         sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
@@ -468,7 +472,7 @@ PROMPT_LOOKUP_NGRAM = 2       # transformers' default max_matching_ngram_size
 
 
 class SpeculativeSession(StreamSession):
-    """StreamSession that verifies draft_tokens drafts per stream and step, greedy only.  tok is
+    """StreamSession that verifies draft_tokens drafts per stream and step, greedy unless sample=True.  tok is
     [B, T] with T = draft_tokens + 1: column 0 is the stream's newest token, columns 1.. are drafts for
     the tokens after it.  A step runs the model on all B T rows in one read of the weights (the window
     is causal within a stream: layer_ops.decode_attention_verify), picks the greedy token of every
@@ -483,9 +487,16 @@ class SpeculativeSession(StreamSession):
     prompt-lookup drafter layer_ops.ngram_draft over the stream's own history with suffixes of up to
     `ngram` tokens.  A subclass may replace it with anything that runs on the device and writes token
     ids of the vocabulary for every stream, live or not (the embedding looks all B T rows up).
-    batch * T is at most core.MT_MAX_TOKENS (the multi-token 4-bit kernel's rows)."""
+    batch * T is at most core.MT_MAX_TOKENS (the multi-token 4-bit kernel's rows).
 
-    def __init__(self, model, batch: int, max_len: int, *, draft_tokens: int = 3, ngram: int = 3, graph: bool = True):
+    sample=True: set_sampling() and seed() as in StreamSession, and a step draws every row with the
+    uniform number of the position it sits at (layer_ops.verify_sample_step_streams): row i of stream
+    b with uniform[b, pos[b] + i].  A token is a function of its logits row and that number, so the
+    emitted tokens are still the same whatever the drafts were, and a stream with temperature <= 0
+    stays greedy.  A step captured while every stream was greedy holds the greedy pick alone."""
+
+    def __init__(self, model, batch: int, max_len: int, *, draft_tokens: int = 3, ngram: int = 3, graph: bool = True,
+                 sample: bool = False):
         from .core import MT_MAX_TOKENS
 
         if int(draft_tokens) < 1:
@@ -498,7 +509,7 @@ class SpeculativeSession(StreamSession):
                              f"multi-token kernels take {MT_MAX_TOKENS}")
         super().__init__(model, batch, max_len, graph=graph)
         dev = self.device
-        self.T, self.ngram = T, int(ngram)
+        self.T, self.ngram, self.sample = T, int(ngram), bool(sample)
         self.tok = torch.zeros((batch, T), dtype=torch.int64, device=dev)
         self.pos_ids = torch.zeros((batch, T), dtype=torch.int64, device=dev)
         self.accepted = torch.zeros(batch, dtype=torch.int32, device=dev)
@@ -507,9 +518,13 @@ class SpeculativeSession(StreamSession):
         self._mask = torch.ones((batch, 1, T, self.max_len), dtype=torch.bool, device=dev)
 
     def set_sampling(self, temperature=None, top_k=None, top_p=None) -> None:
-        """Greedy only: accepting a draft compares it with THE token of its row."""
+        """Without sample=True, greedy only: accepting a draft compares it with THE token of its row.
+        With it, StreamSession's set_sampling: the token of a row is the one its uniform number draws."""
+        if self.sample:
+            return super().set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
         if temperature is not None and bool((torch.as_tensor(temperature, dtype=torch.float32) > 0).any()):
-            raise ValueError("SpeculativeSession: speculative decoding is greedy only (no temperature)")
+            raise ValueError("SpeculativeSession: speculative decoding is greedy only (no temperature) unless the "
+                             "session was opened with sample=True")
 
     def _draft(self) -> None:
         _ops.ngram_draft(self._hist_full, self.pos, self.tok, self.pos_ids, self.ngram)
@@ -519,16 +534,27 @@ class SpeculativeSession(StreamSession):
         # (a stream whose state did not change gets the drafts it had, or others: they are hints)
         r = rows
         first = self.tok[r, :1].contiguous()
-        _ops.greedy_step_streams(logits, self._hist_next[r], self.pos[r], self.live[r], self.stop[r], self.limit[r],
-                                 first)
+        if self._greedy_only:
+            _ops.greedy_step_streams(logits, self._hist_next[r], self.pos[r], self.live[r], self.stop[r],
+                                     self.limit[r], first)
+        else:
+            _ops.sample_step_streams(logits, self._hist_next[r], self.pos[r], self.live[r], self.stop[r],
+                                     self.limit[r], first, self.temperature[r], self.top_k[r], self.top_p[r],
+                                     self._uniform_full[r])
         self.tok[r, :1] = first
         self._draft()
 
     def _step(self) -> None:
         lo = self.model(input_ids=self.tok, past_key_values=self.cache, position_ids=self.pos_ids,
                         attention_mask=self._mask, use_cache=True, _qz_verify_pos=self.pos).logits
-        _ops.verify_step_streams(lo.reshape(self.batch * self.T, -1), self._hist_next, self.pos, self.live, self.stop,
-                                 self.limit, self.tok, self.accepted)
+        lo = lo.reshape(self.batch * self.T, -1)
+        if self._greedy_only:
+            _ops.verify_step_streams(lo, self._hist_next, self.pos, self.live, self.stop, self.limit, self.tok,
+                                     self.accepted)
+        else:
+            _ops.verify_sample_step_streams(lo, self._hist_next, self.pos, self.live, self.stop, self.limit, self.tok,
+                                            self.accepted, self.temperature, self.top_k, self.top_p,
+                                            self._uniform_full)
         self._tokens.add_(self.accepted)
         self._steps.add_(self.accepted.ne(0))
         self._draft()
@@ -543,12 +569,13 @@ class SpeculativeSession(StreamSession):
 
 
 def _speculative_session(model, batch: int, max_len: int, prompt_lookup_num_tokens, max_matching_ngram_size,
-                         do_sample: bool, graph: bool, who: str) -> SpeculativeSession:
-    if do_sample:
+                         do_sample: bool, graph: bool, who: str, sampling: bool = False) -> SpeculativeSession:
+    if do_sample and not sampling:
         raise ValueError(f"{who}: prompt_lookup_num_tokens verifies drafts against the greedy token; "
-                         "do_sample is not supported with it")
+                         "do_sample is not supported with it unless prompt_lookup_sampling=True")
     n = PROMPT_LOOKUP_NGRAM if max_matching_ngram_size is None else int(max_matching_ngram_size)
-    return SpeculativeSession(model, batch, max_len, draft_tokens=int(prompt_lookup_num_tokens), ngram=n, graph=graph)
+    return SpeculativeSession(model, batch, max_len, draft_tokens=int(prompt_lookup_num_tokens), ngram=n, graph=graph,
+                              sample=bool(do_sample and sampling))
 
 
 def _run_speculative(sess: SpeculativeSession, max_new_tokens: int) -> None:
@@ -560,16 +587,20 @@ def _run_speculative(sess: SpeculativeSession, max_new_tokens: int) -> None:
 
 
 def _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attention_mask, graph,
-                          prompt_lookup_num_tokens, max_matching_ngram_size) -> torch.Tensor:
+                          prompt_lookup_num_tokens, max_matching_ngram_size, sampling=None) -> torch.Tensor:
     """generate()'s result from a SpeculativeSession: every stream runs to its EOS or to max_new_tokens,
     then the rows are laid out as the plain loop leaves them -- S + n columns, n the first multiple of
     STOP_CHECK_EVERY by which every stream had its EOS (max_new_tokens if there is none), each
-    stream's tokens after its EOS that EOS."""
+    stream's tokens after its EOS that EOS.  `sampling` (temperature, top_k, top_p, generator) opens
+    the session with sample=True."""
     if attention_mask is not None and not bool(attention_mask.bool().all()):
         raise ValueError("generate: padded prompts are not supported (attention_mask holds a zero)")
     B, S = input_ids.shape
     sess = _speculative_session(model, B, S + max_new_tokens, prompt_lookup_num_tokens, max_matching_ngram_size,
-                                False, graph, "generate")
+                                sampling is not None, graph, "generate", sampling is not None)
+    if sampling is not None:
+        sess.set_sampling(temperature=sampling["temperature"], top_k=sampling["top_k"], top_p=sampling["top_p"])
+        sess.seed(sampling["generator"])
     sess.prefill(input_ids, [S] * B, stop=eos_token_id, max_new_tokens=max_new_tokens)
     _run_speculative(sess, max_new_tokens)
     seqs = sess.sequences()
@@ -589,7 +620,7 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
                     temperature: Union[float, Sequence[float]] = 1.0, top_k: Union[int, Sequence[int]] = 0,
                     top_p: Union[float, Sequence[float]] = 1.0, generator=None, eos_token_id: Optional[int] = None,
                     graph: bool = True, prompt_lookup_num_tokens: Optional[int] = None,
-                    max_matching_ngram_size: Optional[int] = None) -> list:
+                    max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False) -> list:
     """generate() for prompts of different lengths: `prompts` are 1-D int64 tensors; returns one 1-D
     int64 tensor per prompt on the model's device, the prompt followed by up to max_new_tokens picked
     tokens of its own, ending with eos_token_id if the stream picked it.  A stream that stopped writes
@@ -597,7 +628,8 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     One GPU and prepare_for_decode()'s layout; anything else raises.
     prompt_lookup_num_tokens (transformers' name): verify that many prompt-lookup drafts per stream
     and step in a SpeculativeSession (suffixes of up to max_matching_ngram_size tokens, default 2) --
-    greedy only, the same tokens in fewer steps wherever the text repeats itself."""
+    the same tokens in fewer steps wherever the text repeats itself: greedy, or with do_sample and
+    prompt_lookup_sampling=True the sampled tokens of SpeculativeSession(sample=True)."""
     prompts = list(prompts)
     if not prompts or any((not isinstance(p, torch.Tensor)) or p.dim() != 1 or p.numel() < 1 for p in prompts):
         raise ValueError("generate_ragged: prompts must be a non-empty sequence of non-empty 1-D tensors")
@@ -607,7 +639,8 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     B, Smax = len(prompts), max(lens)
     if prompt_lookup_num_tokens is not None:
         sess = _speculative_session(model, B, Smax + max_new_tokens, prompt_lookup_num_tokens,
-                                    max_matching_ngram_size, do_sample, graph, "generate_ragged")
+                                    max_matching_ngram_size, do_sample, graph, "generate_ragged",
+                                    prompt_lookup_sampling)
     elif max_matching_ngram_size is not None:
         raise ValueError("generate_ragged: max_matching_ngram_size needs prompt_lookup_num_tokens")
     else:

@@ -17,6 +17,8 @@ sampled one, which alone has a composed torch route: fp32 or CPU logits).  ``dec
 ``verify_step_streams`` and ``ngram_draft`` are the three launches of a speculative greedy step
 (generation.SpeculativeSession): a window of T tokens per stream, the pick that accepts the longest
 matching prefix of its drafts, and the prompt-lookup drafter; the last two have a composed / host route.
+``verify_sample_step_streams`` is that pick for sampled streams: every row is drawn as
+``sample_step_streams`` would draw it at its position, and a draft is accepted when it is that token.
 
 None of them is in the reference (it leaves them to transformers).  They exist
 because at batch-1 decode the eager torch forms cost ~8, ~10 and 2 dependent
@@ -627,9 +629,33 @@ def _check_verify(name, logits, hist, pos, live, stop, limit, tok, accepted):
 
 def _verify_step_streams_composed(logits, hist, pos, live, stop, limit, tok, accepted) -> None:
     """qz_verify_step_streams' rules in torch ops (no host read): T masked rounds of _feedback_streams."""
+    _accept_streams(logits.argmax(-1).view(tok.shape), hist, pos, live, stop, limit, tok, accepted)
+
+
+def _verify_sample_step_streams_composed(logits, hist, pos, live, stop, limit, tok, accepted, temperature, top_k,
+                                         top_p, uniform) -> None:
+    """qz_verify_sample_step_streams' rules in torch ops (no host read): every row of the window
+    through _sample_step_composed with its stream's parameters and the uniform number of position
+    pos[b] + i (a one-column table, as _sample_step_streams_composed builds it), then the accept loop."""
     B, T = tok.shape
     H = hist.shape[1]
-    g = logits.argmax(-1).view(B, T)
+    R, dev = B * T, logits.device
+    if H:
+        cols = (pos[:, None] + torch.arange(T, device=dev)[None, :]).clamp(0, H - 1)
+        u = uniform.gather(1, cols).reshape(R, 1)
+    else:
+        u = torch.zeros((R, 1), dtype=torch.float32, device=dev)
+    token = torch.zeros(R, dtype=torch.int64, device=dev)
+    _sample_step_composed(logits, torch.zeros((R, 1), dtype=torch.int64, device=dev),
+                          torch.zeros(1, dtype=torch.int64, device=dev), token,
+                          *(t[:, None].expand(B, T).reshape(R) for t in (temperature, top_k, top_p)), u)
+    _accept_streams(token.view(B, T), hist, pos, live, stop, limit, tok, accepted)
+
+
+def _accept_streams(g, hist, pos, live, stop, limit, tok, accepted) -> None:
+    """The accept loop of the verify picks over the rows' tokens g [B, T] (no host read)."""
+    B, T = tok.shape
+    H = hist.shape[1]
     going = live != 0
     p, lv, last = pos.clone(), live.clone(), tok[:, 0].clone()
     n = torch.zeros_like(accepted)
@@ -677,6 +703,44 @@ def verify_step_streams(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Ten
         logits.data_ptr(), _lib.dtype_code(logits.dtype), B, T, V, logits.stride(0), hist.data_ptr(), hist.shape[1],
         hist.shape[1], pos.data_ptr(), live.data_ptr(), stop.data_ptr(), limit.data_ptr(), tok.data_ptr(),
         accepted.data_ptr(), work.data_ptr(), _lib.stream_of(logits)), "qz_verify_step_streams")
+
+
+def verify_sample_step_streams(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, live: torch.Tensor,
+                               stop: torch.Tensor, limit: torch.Tensor, tok: torch.Tensor, accepted: torch.Tensor,
+                               temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+                               uniform: torch.Tensor, *, composed: bool = False) -> None:
+    """The sampled pick that accepts drafts (qz_verify_sample_step_streams): verify_step_streams with
+    g_i := s_i, the token sample_step_streams picks for row b*T + i alone with stream b's
+    temperature / top_k / top_p ([B]) at position pos[b] + i, i.e. with
+    uniform[b, min(max(pos[b] + i, 0), H - 1)] (pos as it is before the call).  s_i depends on the row
+    and on that number alone, so the emitted tokens are those of successive sample_step_streams calls
+    over the same `uniform` whatever the drafts were; a stream with temperature <= 0 gets
+    verify_step_streams' result.  fp32 or CPU logits, or composed=True, take the same rules in torch
+    ops."""
+    name = "verify_sample_step_streams"
+    _check_verify(name, logits, hist, pos, live, stop, limit, tok, accepted)
+    B, T = tok.shape
+    V = logits.shape[1]
+    for t, dt, what in ((temperature, torch.float32, "temperature"), (top_k, torch.int32, "top_k"),
+                        (top_p, torch.float32, "top_p")):
+        if (not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != logits.device or t.shape != (B,)
+                or not t.is_contiguous()):
+            raise ValueError(f"{name}: {what} must be contiguous {dt} [B] on the logits' device")
+    if (not isinstance(uniform, torch.Tensor) or uniform.dtype != torch.float32 or uniform.device != logits.device
+            or uniform.shape != hist.shape or not uniform.is_contiguous()):
+        raise ValueError(f"{name}: uniform must be contiguous float32 [B, H] on the logits' device")
+    if (composed or not logits.is_cuda or logits.dtype not in (torch.float16, torch.bfloat16)
+            or logits.stride(0) < V or B * T > 65535):
+        if B and V:
+            _verify_sample_step_streams_composed(logits, hist, pos, live, stop, limit, tok, accepted, temperature,
+                                                 top_k, top_p, uniform)
+        return
+    work = torch.empty(_lib.lib.qz_verify_sample_step_work_bytes(B, T, V), dtype=torch.uint8, device=logits.device)
+    _lib.check(_lib.lib.qz_verify_sample_step_streams(
+        logits.data_ptr(), _lib.dtype_code(logits.dtype), B, T, V, logits.stride(0), temperature.data_ptr(),
+        top_k.data_ptr(), top_p.data_ptr(), uniform.data_ptr(), uniform.shape[1], hist.data_ptr(), hist.shape[1],
+        hist.shape[1], pos.data_ptr(), live.data_ptr(), stop.data_ptr(), limit.data_ptr(), tok.data_ptr(),
+        accepted.data_ptr(), work.data_ptr(), _lib.stream_of(logits)), "qz_verify_sample_step_streams")
 
 
 def ngram_draft_reference(seq, tok0: int, p: int, T: int, ngram_max: int) -> list:

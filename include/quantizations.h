@@ -471,6 +471,39 @@ int qz_verify_sample_step_streams(const void *logits, int dtype, int B, int T, l
                                   const long long *limit, long long *tok, int *accepted, void *work, void *stream);
 int qz_ngram_draft(int B, int T, int ngram_max, const long long *hist, long long hist_row, long long hist_len,
                    const long long *pos, long long *tok, long long *pos_ids, void *stream);
+/* qz_logits_process: the logits processors of a step, in place on the 16-bit rows the picks above
+ *   read, ONE launch in front of the pick (csrc/logits.hip; one workgroup of 1024 threads per row;
+ *   every array is read on the device, so a captured graph follows new values).  logits [B*T, V] F16/BF16, row stride
+ *   `row` >= V; hist int64 is the sequence itself as qz_ngram_draft takes it; pos int64 with
+ *   pos_stride 0 (one shared position) or 1; tok int64 [B, T], column 0 = s[pos], columns 1.. the
+ *   drafts (NULL allowed when T = 1).  Per-stream arrays, each NULL = off for every stream:
+ *   repetition_penalty / presence_penalty / frequency_penalty fp32 [B], no_repeat_ngram int32 [B],
+ *   min_new_tokens / prompt_len / eos int64 [B] (prompt_len NULL: 0; min length needs eos too).
+ *   Row (b, i), p = pos[b*pos_stride]: the history h is hist[b, 0..p] then tok[b, 1..i], n = p + i + 1
+ *   tokens (row i never sees draft i + 1); c_gen(t) = occurrences of t at indices >= prompt_len[b].
+ *   1. every DISTINCT t in h with 0 <= t < V, once, x = the stored logit in fp32 (a NaN keeps its bits):
+ *      rp != 1: y = x < 0 ? x * rp : x / rp (transformers' rule), else y = x;
+ *      c_gen > 0: y = y - fp * (float)c_gen, then y = y - pp (vLLM's rule, generated tokens only);
+ *      each operation one fp32 rounding, no FMA; y rounded once (nearest even) to the dtype.
+ *   2. g = no_repeat_ngram[b] >= 1: for every k in 0..n-g with h[k..k+g-2] == h[n-g+1..n-1],
+ *      logit[h[k+g-1]] = -inf (g = 1 bans every token seen; g > n bans nothing; no cap on g; the
+ *      comparison crosses from hist into the drafts like any index).
+ *   3. 0 <= eos[b] < V and n - prompt_len[b] < min_new_tokens[b]: logit[eos[b]] = -inf.
+ *   A -inf of 2 or 3 wins over 1 (transformers' order: repetition, no-repeat, min length).  Token ids
+ *   outside [0, V) are skipped; p outside [0, hist_len) leaves the stream's rows untouched; neutral
+ *   values (1, 0, 0, 0, <= 0) leave every bit of the row as it is; nothing but the first V elements of
+ *   the row is written.  The cost follows n, not V (a hash table over the history, in LDS while
+ *   pow2 >= 2 (hist_len + T) <= 16384 slots, else in `work`).  work: qz_logits_process_work_bytes(B, T,
+ *   hist_len) bytes (0: may be NULL), 8-B aligned, any content.  QZ_ERR_ARG: NULL logits/hist/pos, a
+ *   negative size, row < V, hist_row < hist_len, pos_stride not 0 or 1, T > 1 without tok, a missing
+ *   work; QZ_ERR_DTYPE: not F16/BF16; QZ_ERR_SHAPE: T > 16, B*T > 65535, V or hist_len >= 2^31; B, T or
+ *   V of 0 is QZ_OK with nothing launched. */
+long long qz_logits_process_work_bytes(int B, int T, long long hist_len);
+int qz_logits_process(void *logits, int dtype, int B, int T, long long V, long long row, const long long *hist,
+                      long long hist_row, long long hist_len, const long long *pos, long long pos_stride,
+                      const long long *tok, const float *repetition_penalty, const float *presence_penalty,
+                      const float *frequency_penalty, const int *no_repeat_ngram, const long long *min_new_tokens,
+                      const long long *prompt_len, const long long *eos, void *work, void *stream);
 /* qz_gemv_dense: the model's fp16/bf16 lm_head for one decode token (transformers keeps it
  *   unquantised): y[m] = sum_k W[m*K + k] x[k] for m < M, fp32 accumulation, rounded once to
  *   dtype; K in {4096, 8192}, W and x 16-B aligned (else QZ_ERR_SHAPE, nothing launched). */

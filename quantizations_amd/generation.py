@@ -9,7 +9,10 @@ DecodeSession / generate() take equal-length prompts and move every stream toget
 finished stream's row handed to the next prompt without recapturing).  SpeculativeSession /
 prompt_lookup_num_tokens= verify prompt-lookup drafts: several tokens per stream and step, the
 same tokens in fewer reads of the weights -- greedy, or with sample=True / prompt_lookup_sampling=True
-the tokens each position's uniform number draws.  One GPU only; no penalties, no beams.
+the tokens each position's uniform number draws.  set_penalties() / repetition_penalty=,
+presence_penalty=, frequency_penalty=, no_repeat_ngram_size=, min_new_tokens= put
+layer_ops.process_logits in front of every pick, inside the captured step: the processors read each
+stream's history and their own parameters on the device.  One GPU only; no beams.
 """
 from __future__ import annotations
 
@@ -58,12 +61,35 @@ def _per_stream(value, batch: int, dtype, device, name: str) -> torch.Tensor:
     return t.to(device)
 
 
+_PENALTIES = (   # set_penalties()' argument, the session's buffer, its dtype, the neutral value
+    ("repetition_penalty", "repetition_penalty", torch.float32, 1),
+    ("presence_penalty", "presence_penalty", torch.float32, 0),
+    ("frequency_penalty", "frequency_penalty", torch.float32, 0),
+    ("no_repeat_ngram_size", "no_repeat_ngram", torch.int32, 0),
+    ("min_new_tokens", "min_new_tokens", torch.int64, 0),
+)
+
+
+def _penalty_buffers(sess, batch: int, dev) -> None:
+    """The processors' device buffers, neutral, and the host's knowledge of them."""
+    sess.repetition_penalty = torch.ones(batch, dtype=torch.float32, device=dev)
+    sess.presence_penalty = torch.zeros(batch, dtype=torch.float32, device=dev)
+    sess.frequency_penalty = torch.zeros(batch, dtype=torch.float32, device=dev)
+    sess.no_repeat_ngram = torch.zeros(batch, dtype=torch.int32, device=dev)
+    sess.min_new_tokens = torch.zeros(batch, dtype=torch.int64, device=dev)
+    sess.prompt_len = torch.zeros(batch, dtype=torch.int64, device=dev)
+    sess._neutral = {name: True for name, _, _, _ in _PENALTIES}
+    sess._processing = False   # host knowledge: some processor is on, so the step holds process_logits
+
+
 class DecodeSession:
     """One batch of decode streams over `model`: the StaticCache and the static buffers a captured
     step reads and writes -- tok [B, 1], pos [1], hist [B, max_len] (int64), uniform [B, max_len],
-    temperature / top_p [B] (float32), top_k [B] (int32).  hist holds the sequence itself (prompt,
-    then the picked tokens); pos is the position of `tok`, the newest token, which the next step feeds:
-    that step writes its pick to hist[:, pos + 1], drawing it with uniform[:, pos], and advances
+    temperature / top_p [B] (float32), top_k [B] (int32), and the processors' repetition_penalty /
+    presence_penalty / frequency_penalty [B] (float32), no_repeat_ngram [B] (int32), min_new_tokens /
+    prompt_len / stop [B] (int64; stop is the EOS min_new_tokens holds back, -1: none).  hist holds
+    the sequence itself (prompt, then the picked tokens); pos is the position of `tok`, the newest
+    token, which the next step feeds: that step writes its pick to hist[:, pos + 1], drawing it with uniform[:, pos], and advances
     pos.  prefill() runs the prompt and picks the first new token."""
 
     def __init__(self, model, batch: int, max_len: int, *, graph: bool = True):
@@ -92,6 +118,8 @@ class DecodeSession:
         self.temperature = torch.zeros(batch, dtype=torch.float32, device=dev)   # greedy until set_sampling
         self.top_k = torch.zeros(batch, dtype=torch.int32, device=dev)
         self.top_p = torch.ones(batch, dtype=torch.float32, device=dev)
+        self.stop = torch.full((batch,), -1, dtype=torch.int64, device=dev)
+        _penalty_buffers(self, batch, dev)
         self._pos_ids = self.pos.view(1, 1).expand(batch, 1)
         self._graph = None
         self._greedy_only = True   # host knowledge: no stream has a temperature > 0
@@ -115,6 +143,49 @@ class DecodeSession:
         if top_p is not None:
             self.top_p.copy_(_per_stream(top_p, self.batch, torch.float32, self.device, "top_p"))
 
+    def set_penalties(self, repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
+                      no_repeat_ngram_size=None, min_new_tokens=None) -> None:
+        """Scalars or one value per stream, written in place like set_sampling: repetition_penalty > 0
+        (transformers' rule over every token of the history; 1: off), presence_penalty /
+        frequency_penalty (vLLM's rule over the generated tokens; 0: off), no_repeat_ngram_size >= 0 (0:
+        off), min_new_tokens >= 0 (holds the stream's `stop` token back; 0: off).  The next step, replayed
+        or not, uses them.  A graph captured while every value was neutral holds no processing launch, so
+        a processor cannot be switched on after that capture; one captured with any processor on follows
+        every later change, back to neutral included."""
+        given = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                     frequency_penalty=frequency_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                     min_new_tokens=min_new_tokens)
+        new = {}
+        for name, buf, dt, neutral in _PENALTIES:
+            if given[name] is None:
+                continue
+            t = _per_stream(given[name], self.batch, dt, "cpu", name)
+            if dt == torch.float32 and not bool(torch.isfinite(t).all()):
+                raise ValueError(f"set_penalties: {name} must be finite")
+            if name == "repetition_penalty" and not bool((t > 0).all()):
+                raise ValueError("set_penalties: repetition_penalty must be positive")
+            if name in ("no_repeat_ngram_size", "min_new_tokens") and bool((t < 0).any()):
+                raise ValueError(f"set_penalties: {name} must not be negative")
+            new[name] = (buf, t, bool((t == neutral).all()))
+        if self._graph is not None and not self._processing and not all(n for _, _, n in new.values()):
+            raise ValueError("set_penalties: this session captured a step without logits processing")
+        for name, (buf, t, neutral) in new.items():
+            getattr(self, buf).copy_(t)
+            self._neutral[name] = neutral
+        if self._graph is None:
+            self._processing = not all(self._neutral.values())
+
+    def _process(self, logits: torch.Tensor, rows: slice = slice(None), tok: Optional[torch.Tensor] = None) -> None:
+        """layer_ops.process_logits in front of a pick, when some processor is on: in place on the
+        rows the pick reads (logits [B, V], or [B*T, V] with the window's tok [B, T])."""
+        if not self._processing:
+            return
+        r = rows
+        _ops.process_logits(logits, self._hist_full[r], self.pos if self.pos.numel() == 1 else self.pos[r], tok,
+                            repetition_penalty=self.repetition_penalty[r], presence_penalty=self.presence_penalty[r],
+                            frequency_penalty=self.frequency_penalty[r], no_repeat_ngram=self.no_repeat_ngram[r],
+                            min_new_tokens=self.min_new_tokens[r], prompt_len=self.prompt_len[r], eos=self.stop[r])
+
     def seed(self, generator: Union[torch.Generator, int, None]) -> None:
         """Refill `uniform` (one number in [0, 1) per stream and position) with torch.rand; the token
         at sequence index i is drawn with uniform[:, i - 1]."""
@@ -126,6 +197,7 @@ class DecodeSession:
             self.uniform.copy_(torch.rand(self.uniform.shape, generator=generator, device=generator.device))
 
     def _pick(self, logits: torch.Tensor) -> None:
+        self._process(logits)
         if self._greedy_only and logits.is_cuda:
             _ops.greedy_step(logits, self._hist_next, self.pos, self.tok)
         else:
@@ -147,6 +219,7 @@ class DecodeSession:
         ids = input_ids.to(self.device)
         self.hist[:, :S] = ids
         self.pos.fill_(S - 1)                          # the last prompt token; the pick makes it S
+        self.prompt_len.fill_(S)
         out = self.model(input_ids=ids, past_key_values=self.cache,
                          cache_position=torch.arange(S, device=self.device), use_cache=True)
         self._pick(out.logits[:, -1])
@@ -210,7 +283,9 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
              top_p: Union[float, Sequence[float]] = 1.0, generator=None, eos_token_id: Optional[int] = None,
              attention_mask: Optional[torch.Tensor] = None, graph: bool = True,
              prompt_lookup_num_tokens: Optional[int] = None,
-             max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False) -> torch.Tensor:
+             max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False,
+             repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
+             no_repeat_ngram_size=None, min_new_tokens=None) -> torch.Tensor:
     """input_ids [B, S] (equal-length prompts) followed by up to max_new_tokens picked tokens per
     stream: greedy, or with do_sample temperature / top_k / top_p (scalars or one per stream; a
     temperature <= 0 keeps that stream greedy) drawn from `generator` (a torch.Generator or a seed).
@@ -222,7 +297,11 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
     Greedy unless prompt_lookup_sampling=True, which with do_sample accepts a draft when it is the token
     the row's uniform number draws (SpeculativeSession(sample=True): the tokens of the one-token sampler
     over the same numbers, whatever the drafts).  It needs prepare_for_decode()'s layout on one GPU; the
-    result has the shape and the EOS fill the plain call defines."""
+    result has the shape and the EOS fill the plain call defines.
+    repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size, min_new_tokens
+    (scalars or one per stream; None: off): set_penalties() -- the processors run inside the step, in
+    front of the pick, with or without prompt lookup; min_new_tokens holds eos_token_id back and does
+    nothing without one."""
     if input_ids.dim() != 2:
         raise ValueError("generate: input_ids must be [B, S]")
     B, S = input_ids.shape
@@ -233,11 +312,17 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
                          "do_sample is not supported with it unless prompt_lookup_sampling=True")
     if max_new_tokens < 1:
         return input_ids.clone()
+    penalties = _given_penalties(repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size,
+                                 min_new_tokens)
     if prompt_lookup_num_tokens is not None:
         sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator) if do_sample else None
         return _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attention_mask, graph,
-                                     prompt_lookup_num_tokens, max_matching_ngram_size, sampling)
+                                     prompt_lookup_num_tokens, max_matching_ngram_size, sampling, penalties)
     sess = DecodeSession(model, B, S + max_new_tokens, graph=graph)
+    if penalties:
+        sess.set_penalties(**penalties)
+        if eos_token_id is not None:
+            sess.stop.fill_(int(eos_token_id))
     if do_sample:
         sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
         sess.seed(generator)
@@ -258,6 +343,15 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
     return out
 
 
+def _given_penalties(repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size,
+                     min_new_tokens) -> dict:
+    """The processor arguments a caller passed, as set_penalties() takes them (empty: none)."""
+    given = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                 frequency_penalty=frequency_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                 min_new_tokens=min_new_tokens)
+    return {k: v for k, v in given.items() if v is not None}
+
+
 def _single_gpu_prepared(model, who: str) -> torch.device:
     """The model's device if it is one GPU and prepare_for_decode() laid the model out; raises otherwise."""
     devices = {p.device for p in model.parameters()} | {b.device for b in model.buffers()}
@@ -276,7 +370,8 @@ class StreamSession:
     """`batch` decode streams over `model`, each at its own position: the StaticCache
     ([B, Hkv, max_len, D] per layer) and the static buffers a captured step reads and writes -- tok
     [B, 1], pos [B], stop [B], limit [B] (int64), live [B] (int32), hist [B, max_len] (int64),
-    uniform [B, max_len], temperature / top_p [B] (float32), top_k [B] (int32).
+    uniform [B, max_len], temperature / top_p [B] (float32), top_k [B] (int32), and DecodeSession's
+    processor buffers (set_penalties; min_new_tokens holds stop[b] back).
 
     hist[b] is stream b's sequence; pos[b] is the index of tok[b], its newest token, which the next
     step feeds: that step writes k/v to cache slot pos[b], attends to slots 0..pos[b], writes its pick
@@ -314,6 +409,7 @@ class StreamSession:
         self.temperature = torch.zeros(batch, dtype=torch.float32, device=dev)   # greedy until set_sampling
         self.top_k = torch.zeros(batch, dtype=torch.int32, device=dev)
         self.top_p = torch.ones(batch, dtype=torch.float32, device=dev)
+        _penalty_buffers(self, batch, dev)
         self._pos_ids = self.pos.view(batch, 1)
         # a constant 4-D bool mask: create_causal_mask hands a 4-D mask back as it is (no launch),
         # and decode_attention_streams takes none -- visibility is j <= pos[b]
@@ -323,10 +419,13 @@ class StreamSession:
         self._prefilled = False
 
     set_sampling = DecodeSession.set_sampling
+    set_penalties = DecodeSession.set_penalties
+    _process = DecodeSession._process
     seed = DecodeSession.seed
 
     def _pick(self, logits: torch.Tensor, rows: slice = slice(None)) -> None:
         r = rows
+        self._process(logits, r)
         if self._greedy_only:
             _ops.greedy_step_streams(logits, self._hist_next[r], self.pos[r], self.live[r], self.stop[r],
                                      self.limit[r], self.tok[r])
@@ -369,6 +468,7 @@ class StreamSession:
         real = torch.arange(Smax, device=dev)[None, :] < ln[:, None]
         self._hist_full[:, :Smax] = torch.where(real, ids, self._hist_full[:, :Smax])
         self.pos.copy_(ln - 1)
+        self.prompt_len.copy_(ln)
         self.limit.copy_(torch.tensor(limits, device=dev))
         self.stop.copy_(_per_stream(-1 if stop is None else stop, B, torch.int64, dev, "stop"))
         self.live.fill_(1)
@@ -407,6 +507,7 @@ class StreamSession:
             mine.values[b, :, :S].copy_(theirs.values[0, :, :S])
         self._hist_full[b, :S] = ids[0]
         self.pos[b] = S - 1
+        self.prompt_len[b] = S
         self.stop[b] = -1 if stop is None else int(stop)
         self.limit[b] = limit
         self.live[b] = 1    # before the pick, which writes live streams only and may retire this one at once
@@ -493,7 +594,11 @@ class SpeculativeSession(StreamSession):
     uniform number of the position it sits at (layer_ops.verify_sample_step_streams): row i of stream
     b with uniform[b, pos[b] + i].  A token is a function of its logits row and that number, so the
     emitted tokens are still the same whatever the drafts were, and a stream with temperature <= 0
-    stays greedy.  A step captured while every stream was greedy holds the greedy pick alone."""
+    stays greedy.  A step captured while every stream was greedy holds the greedy pick alone.
+
+    set_penalties(): the processors run over all B T rows in one launch before the pick, row i with the
+    history hist[b, :pos[b] + 1] followed by the drafts 1..i.  An emitted row's drafts are the tokens
+    emitted before it, so its history is the real one and the tokens stay StreamSession's."""
 
     def __init__(self, model, batch: int, max_len: int, *, draft_tokens: int = 3, ngram: int = 3, graph: bool = True,
                  sample: bool = False):
@@ -533,6 +638,7 @@ class SpeculativeSession(StreamSession):
         # prefill() and admit(): one row of logits per stream, the plain pick, then drafts for everyone
         # (a stream whose state did not change gets the drafts it had, or others: they are hints)
         r = rows
+        self._process(logits, r)
         first = self.tok[r, :1].contiguous()
         if self._greedy_only:
             _ops.greedy_step_streams(logits, self._hist_next[r], self.pos[r], self.live[r], self.stop[r],
@@ -548,6 +654,7 @@ class SpeculativeSession(StreamSession):
         lo = self.model(input_ids=self.tok, past_key_values=self.cache, position_ids=self.pos_ids,
                         attention_mask=self._mask, use_cache=True, _qz_verify_pos=self.pos).logits
         lo = lo.reshape(self.batch * self.T, -1)
+        self._process(lo, tok=self.tok)    # row i sees the drafts 1..i it was fed after
         if self._greedy_only:
             _ops.verify_step_streams(lo, self._hist_next, self.pos, self.live, self.stop, self.limit, self.tok,
                                      self.accepted)
@@ -587,12 +694,13 @@ def _run_speculative(sess: SpeculativeSession, max_new_tokens: int) -> None:
 
 
 def _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attention_mask, graph,
-                          prompt_lookup_num_tokens, max_matching_ngram_size, sampling=None) -> torch.Tensor:
+                          prompt_lookup_num_tokens, max_matching_ngram_size, sampling=None,
+                          penalties=None) -> torch.Tensor:
     """generate()'s result from a SpeculativeSession: every stream runs to its EOS or to max_new_tokens,
     then the rows are laid out as the plain loop leaves them -- S + n columns, n the first multiple of
     STOP_CHECK_EVERY by which every stream had its EOS (max_new_tokens if there is none), each
     stream's tokens after its EOS that EOS.  `sampling` (temperature, top_k, top_p, generator) opens
-    the session with sample=True."""
+    the session with sample=True; `penalties` is set_penalties()' arguments."""
     if attention_mask is not None and not bool(attention_mask.bool().all()):
         raise ValueError("generate: padded prompts are not supported (attention_mask holds a zero)")
     B, S = input_ids.shape
@@ -601,6 +709,8 @@ def _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attent
     if sampling is not None:
         sess.set_sampling(temperature=sampling["temperature"], top_k=sampling["top_k"], top_p=sampling["top_p"])
         sess.seed(sampling["generator"])
+    if penalties:
+        sess.set_penalties(**penalties)
     sess.prefill(input_ids, [S] * B, stop=eos_token_id, max_new_tokens=max_new_tokens)
     _run_speculative(sess, max_new_tokens)
     seqs = sess.sequences()
@@ -620,7 +730,9 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
                     temperature: Union[float, Sequence[float]] = 1.0, top_k: Union[int, Sequence[int]] = 0,
                     top_p: Union[float, Sequence[float]] = 1.0, generator=None, eos_token_id: Optional[int] = None,
                     graph: bool = True, prompt_lookup_num_tokens: Optional[int] = None,
-                    max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False) -> list:
+                    max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False,
+                    repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
+                    no_repeat_ngram_size=None, min_new_tokens=None) -> list:
     """generate() for prompts of different lengths: `prompts` are 1-D int64 tensors; returns one 1-D
     int64 tensor per prompt on the model's device, the prompt followed by up to max_new_tokens picked
     tokens of its own, ending with eos_token_id if the stream picked it.  A stream that stopped writes
@@ -629,7 +741,9 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     prompt_lookup_num_tokens (transformers' name): verify that many prompt-lookup drafts per stream
     and step in a SpeculativeSession (suffixes of up to max_matching_ngram_size tokens, default 2) --
     the same tokens in fewer steps wherever the text repeats itself: greedy, or with do_sample and
-    prompt_lookup_sampling=True the sampled tokens of SpeculativeSession(sample=True)."""
+    prompt_lookup_sampling=True the sampled tokens of SpeculativeSession(sample=True).
+    repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size, min_new_tokens:
+    as generate() takes them, one value or one per prompt."""
     prompts = list(prompts)
     if not prompts or any((not isinstance(p, torch.Tensor)) or p.dim() != 1 or p.numel() < 1 for p in prompts):
         raise ValueError("generate_ragged: prompts must be a non-empty sequence of non-empty 1-D tensors")
@@ -648,6 +762,10 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     if do_sample:
         sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
         sess.seed(generator)
+    penalties = _given_penalties(repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size,
+                                 min_new_tokens)
+    if penalties:
+        sess.set_penalties(**penalties)
     ids = torch.zeros((B, Smax), dtype=torch.int64, device=sess.device)
     for b, p in enumerate(prompts):
         ids[b, :lens[b]] = p.to(sess.device)

@@ -743,6 +743,130 @@ def verify_sample_step_streams(logits: torch.Tensor, hist: torch.Tensor, pos: to
         accepted.data_ptr(), work.data_ptr(), _lib.stream_of(logits)), "qz_verify_sample_step_streams")
 
 
+_PROCESS_PARAMS = (("repetition_penalty", torch.float32), ("presence_penalty", torch.float32),
+                   ("frequency_penalty", torch.float32), ("no_repeat_ngram", torch.int32),
+                   ("min_new_tokens", torch.int64), ("prompt_len", torch.int64), ("eos", torch.int64))
+
+
+def process_logits_supported(logits: torch.Tensor) -> bool:
+    """What qz_logits_process takes: fp16 / bf16 logits [R, V] on the GPU with unit element stride and
+    a row stride of at least V, at most 65535 rows.  Metadata only."""
+    return (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype in (torch.float16, torch.bfloat16)
+            and logits.dim() == 2 and logits.stride(-1) == 1 and logits.stride(0) >= logits.shape[1]
+            and logits.shape[0] <= 65535 and logits.shape[1] < 2 ** 31)
+
+
+def _process_logits_composed(logits, hist, pos, tok, T, params) -> None:
+    """qz_logits_process' rules with the bookkeeping on the host (one read of hist, pos, tok and the
+    parameters) and the arithmetic in torch ops on the logits' device: the same fp32 operations,
+    rounded once to the logits' dtype (for fp32 logits that rounding is the identity)."""
+    B, H = hist.shape
+    V = logits.shape[1]
+    h_all, ps = hist.cpu().tolist(), pos.cpu().reshape(-1).tolist()
+    drafts = tok.cpu().reshape(B, T).tolist() if tok is not None else None
+    host = {k: (v.cpu().tolist() if v is not None else None) for k, v in params.items()}
+
+    def val(name, b, default):
+        return default if host[name] is None else host[name][b]
+
+    dev = logits.device
+    ninf = float("-inf")
+    for b in range(B):
+        p = ps[b if len(ps) > 1 else 0]
+        if not 0 <= p < H:
+            continue
+        rp, pp, fp = val("repetition_penalty", b, 1.0), val("presence_penalty", b, 0.0), val("frequency_penalty", b, 0.0)
+        g, pl = val("no_repeat_ngram", b, 0), val("prompt_len", b, 0)
+        mn = val("min_new_tokens", b, 0) if host["eos"] is not None else 0
+        pen = rp != 1.0 or pp != 0.0 or fp != 0.0
+        if not pen and g <= 0 and mn <= 0:
+            continue
+        for i in range(T):
+            h = h_all[b][:p + 1] + (drafts[b][1:i + 1] if i else [])
+            n = len(h)
+            row = logits[b * T + i]
+            banned = set()
+            if 1 <= g <= n:
+                tail = h[n - g + 1:]
+                banned = {h[k + g - 1] for k in range(n - g + 1) if h[k:k + g - 1] == tail}
+            if mn > 0 and n - pl < mn:
+                banned.add(host["eos"][b])
+            banned = sorted(t for t in banned if 0 <= t < V)
+            if pen:
+                cnt = {}
+                for k, t in enumerate(h):
+                    if 0 <= t < V:
+                        cnt[t] = cnt.get(t, 0) + (1 if k >= pl else 0)
+                ids = torch.tensor(list(cnt.keys()), dtype=torch.int64, device=dev)
+                c = torch.tensor(list(cnt.values()), dtype=torch.float32, device=dev)
+                old = row[ids]
+                x = old.float()
+                f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)   # noqa: E731
+                y = torch.where(x < 0, x * f32(rp), x / f32(rp)) if rp != 1.0 else x
+                y = torch.where(c > 0, (y - f32(fp) * c) - f32(pp), y)
+                out = torch.where(torch.isnan(y), torch.full_like(y, float("nan")), y).to(row.dtype)
+                row[ids] = torch.where(torch.isnan(x), old, out)    # a NaN logit keeps its bits
+            if banned:
+                row[torch.tensor(banned, dtype=torch.int64, device=dev)] = ninf
+
+
+def process_logits(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, tok: Optional[torch.Tensor] = None, *,
+                   repetition_penalty: Optional[torch.Tensor] = None, presence_penalty: Optional[torch.Tensor] = None,
+                   frequency_penalty: Optional[torch.Tensor] = None, no_repeat_ngram: Optional[torch.Tensor] = None,
+                   min_new_tokens: Optional[torch.Tensor] = None, prompt_len: Optional[torch.Tensor] = None,
+                   eos: Optional[torch.Tensor] = None, composed: bool = False) -> None:
+    """The logits processors of a step, in place, in front of a pick (qz_logits_process;
+    include/quantizations.h states the rules).  logits [B*T, V]; hist int64 [B, H] is the sequence
+    itself (ngram_draft's operand, not the picks' shifted one); pos int64 [1] (one position for all) or
+    [B]; tok int64 [B, T] (column 0 = hist[b, pos[b]], columns 1.. the drafts) -- None, or [B] / [B, 1],
+    means T = 1.  Row (b, i) has the history hist[b, :pos[b] + 1] + tok[b, 1:i + 1].  Per stream, each
+    None = off: repetition_penalty (transformers' rule, every distinct token of the history once),
+    presence_penalty / frequency_penalty (float32 [B]; vLLM's rule over the tokens at indices >=
+    prompt_len[b]), no_repeat_ngram (int32 [B]; banned tokens become -inf), min_new_tokens / prompt_len /
+    eos (int64 [B]: eos[b] is -inf while fewer than min_new_tokens[b] tokens follow the prompt).
+    Neutral values (1, 0, 0, 0, 0) leave every bit as it is.  Every value is read on the device, so a
+    captured call follows in-place changes.  fp32 or CPU logits (process_logits_supported is false),
+    or composed=True, take the same rules with the bookkeeping on the host (not capturable)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.stride(-1) != 1:
+        raise ValueError("process_logits: logits must be [B*T, V] with unit element stride")
+    for t, what in ((hist, "hist"), (pos, "pos")) + (((tok, "tok"),) if tok is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.device != logits.device or not t.is_contiguous():
+            raise ValueError(f"process_logits: {what} must be contiguous int64 on the logits' device")
+    if hist.dim() != 2:
+        raise ValueError("process_logits: hist must be [B, H]")
+    B, H = hist.shape
+    T = 1
+    if tok is not None:
+        if tok.dim() == 2 and tok.shape[0] == B:
+            T = tok.shape[1]
+        elif tok.shape != (B,):
+            raise ValueError("process_logits: tok must be [B, T] (or [B])")
+    if not 1 <= T <= VERIFY_MAX_T:
+        raise ValueError(f"process_logits: T must be in 1..{VERIFY_MAX_T}")
+    R, V = logits.shape
+    if R != B * T or pos.numel() not in (1, B):
+        raise ValueError("process_logits: logits [B*T, V], pos [1] or [B]")
+    params = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                  frequency_penalty=frequency_penalty, no_repeat_ngram=no_repeat_ngram, min_new_tokens=min_new_tokens,
+                  prompt_len=prompt_len, eos=eos)
+    for name, dt in _PROCESS_PARAMS:
+        t = params[name]
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != logits.device
+                              or t.shape != (B,) or not t.is_contiguous()):
+            raise ValueError(f"process_logits: {name} must be contiguous {dt} [B] on the logits' device")
+    if not (B and V):
+        return
+    if composed or not process_logits_supported(logits):
+        _process_logits_composed(logits, hist, pos, tok if T > 1 else None, T, params)
+        return
+    work = torch.empty(_lib.lib.qz_logits_process_work_bytes(B, T, H), dtype=torch.uint8, device=logits.device)
+    _lib.check(_lib.lib.qz_logits_process(
+        logits.data_ptr(), _lib.dtype_code(logits.dtype), B, T, V, logits.stride(0), hist.data_ptr(), H, H,
+        pos.data_ptr(), 0 if pos.numel() == 1 and B > 1 else 1, _lib.ptr(tok) if T > 1 else 0,
+        *(_lib.ptr(params[name]) for name, _ in _PROCESS_PARAMS), work.data_ptr() if work.numel() else 0,
+        _lib.stream_of(logits)), "qz_logits_process")
+
+
 def ngram_draft_reference(seq, tok0: int, p: int, T: int, ngram_max: int) -> list:
     """The drafter's rule on host integers: seq[0..p] is the stream's history (seq[p] the newest
     token), the result its T - 1 drafts."""

@@ -372,6 +372,33 @@ int qz_decode_attention_verify(int dtype, int B, int T, int Hq, int Hkv, int D, 
                                const void *sin, long long cs_row, void *k_cache, void *v_cache,
                                const long long *pos, void *out, long long out_row, float *work, float scale,
                                void *stream);
+/* Prefill attention: a window of up to T new tokens per stream against the static cache, O(visible
+ * keys), tiled on the matrix cores (csrc/prefill_attn.hip).  q/out have B*T rows, k/v B*T rows,
+ * cos/sin one row per token row (row stride cs_row >= D); pos and len are int64 [B] (device, read
+ * only, never written).  Token row r = b*T + i with i < len[b] sits at position pos[b] + i:
+ *   - its rotated k (qz_decode_attention_verify's arithmetic: the cache receives the bits a decode
+ *     step at that position stores) and its v go to that slot of cache row b, and it sees keys
+ *     0 .. pos[b] + i of that cache row, the window's earlier rows included;
+ *   - rows with i >= len[b] (padding; len[b] = 0: the stream is idle) write nothing to the caches,
+ *     are never read (any garbage is fine) and their output rows are zeros, whatever pos[b] is;
+ *   - pos[b] < 0 or pos[b] >= L makes the len[b] real rows of stream b NaN and writes nothing; a real
+ *     row with pos[b] + i >= L is NaN and writes nothing, the rows before it are intact; other
+ *     streams are unaffected;
+ *   - a row's output bits depend on its own q/cos/sin row, its position and cache row b only: not
+ *     on T, on i, on the other streams or on len -- a window split into several calls gives the
+ *     bits of the whole window.  Cache rows above the last position written may hold anything, NaN
+ *     included.
+ * Scores are fp32 (v_mfma_f32_16x16x32), scale applied to the fp32 score, online softmax in fp32
+ * over key tiles of 64 from absolute position 0, probabilities rounded once to `dtype` for P V,
+ * output accumulated in fp32, divided by the fp32 row sum and rounded once.  No workspace.
+ * Two launches (the k/v write, the attention).  F16/BF16, D in {64, 128}, Hq/Hkv <= 8, T >= 1,
+ * B, Hq <= 65535 (QZ_ERR_SHAPE / QZ_ERR_DTYPE otherwise, nothing launched); q, cos, sin and the
+ * caches 16-B aligned with q_row, cs_row multiples of 8; out 8-B aligned with out_row a multiple
+ * of 4; v 4-B aligned with an even v_row (QZ_ERR_ARG).  B, T or Hq of 0: QZ_OK, nothing done. */
+int qz_prefill_attention(int dtype, int B, int T, int Hq, int Hkv, int D, int L, const void *q, long long q_row,
+                         const void *k, long long k_row, const void *v, long long v_row, const void *cos,
+                         const void *sin, long long cs_row, void *k_cache, void *v_cache, const long long *pos,
+                         const long long *len, void *out, long long out_row, float scale, void *stream);
 
 /* Decode-step glue of the host model (transformers' LlamaModel.forward), one launch each in place
  * of the small torch kernels it issues per step.  Not part of the Linear4bit path; the

@@ -379,11 +379,19 @@ class StreamSession:
     (live[b] = 0) after writing its stop token or once pos[b] reaches limit[b]; from then on the
     step writes nothing of it, and admit() may hand its row to another prompt.  The graph is
     captured once: positions, liveness, stop tokens, limits and sampling parameters are all read on
-    the device."""
+    the device.
 
-    def __init__(self, model, batch: int, max_len: int, *, graph: bool = True):
+    prefill_chunk (None: everything as it was): an int c >= 1 runs prompts through
+    layer_ops.prefill_attention in windows of c tokens, one model forward per window -- attention
+    over the visible keys only, no [T, max_len] mask, activations sized by c, the lm_head on one row
+    per stream -- lets admit() write straight into row b of the session's cache, and opens extend()."""
+
+    def __init__(self, model, batch: int, max_len: int, *, graph: bool = True, prefill_chunk: Optional[int] = None):
         if batch < 1 or max_len < 2:
             raise ValueError("StreamSession: batch must be positive and max_len at least 2")
+        if prefill_chunk is not None and int(prefill_chunk) < 1:
+            raise ValueError("StreamSession: prefill_chunk must be None or at least 1")
+        self.prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
         self.device = _single_gpu_prepared(model, "StreamSession")
         from transformers.cache_utils import StaticCache
 
@@ -442,6 +450,44 @@ class StreamSession:
                              f"asked for {n}")
         return length + n - 1   # the stream leaves once pos reaches it: length + n tokens in hist
 
+    def _init_cache(self) -> None:
+        """Chunk mode: lay the StaticCache out before the first window (nothing calls its update())."""
+        cfg = self.model.config
+        head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
+        dtype = self.model.get_input_embeddings().weight.dtype
+        self.cache.early_initialization(self.batch, cfg.num_key_value_heads, head_dim, dtype, self.device)
+
+    def _windows(self, ids: torch.Tensor, counts, row0: int, start: int) -> torch.Tensor:
+        """Chunk mode: run ids [nb, S] (stream r's first counts[r] columns are real) at positions
+        start, start + 1, ... of cache rows row0 .. row0 + nb - 1, in windows of prefill_chunk columns,
+        one decoder forward each (windows past the longest count are not run).  Returns the decoder's
+        last hidden state at each stream's last real token, [nb, H]."""
+        c, dev = self.prefill_chunk, self.device
+        nb = ids.shape[0]
+        n = torch.as_tensor(counts, dtype=torch.int64, device=dev).reshape(nb)
+        top = int(max(counts))
+        decoder = self.model.get_decoder()
+        one = torch.ones(1, dtype=torch.bool, device=dev)
+        rows = torch.arange(nb, device=dev)
+        last = None
+        for s0 in range(0, top, c):
+            T = min(c, top - s0)
+            pos = torch.full((nb,), start + s0, dtype=torch.int64, device=dev)
+            length = (n - s0).clamp(0, T)
+            pids = (start + s0 + torch.arange(T, device=dev)).unsqueeze(0).expand(nb, T).contiguous()
+            # create_causal_mask hands a 4-D mask back as it is: an expanded view of one element
+            h = decoder(input_ids=ids[:, s0:s0 + T], past_key_values=self.cache, position_ids=pids,
+                        attention_mask=one.expand(nb, 1, T, self.max_len), use_cache=True,
+                        _qz_prefill=(pos, length, int(row0))).last_hidden_state
+            idx = n - 1 - s0
+            mine = h[rows, idx.clamp(0, T - 1)]
+            last = mine if last is None else torch.where(((idx >= 0) & (idx < T))[:, None], mine, last)
+        return last
+
+    def _head(self, hidden: torch.Tensor) -> torch.Tensor:
+        """lm_head on one row per stream: [nb, H] -> [nb, V]."""
+        return self.model.get_output_embeddings()(hidden.unsqueeze(1))[:, 0]
+
     @torch.inference_mode()
     def prefill(self, input_ids: torch.Tensor, lengths, *, stop=None, max_new_tokens=None) -> None:
         """Run right-padded prompts (input_ids [B, Smax], stream b's prompt in its first lengths[b]
@@ -472,6 +518,11 @@ class StreamSession:
         self.limit.copy_(torch.tensor(limits, device=dev))
         self.stop.copy_(_per_stream(-1 if stop is None else stop, B, torch.int64, dev, "stop"))
         self.live.fill_(1)
+        if self.prefill_chunk is not None:
+            self._init_cache()
+            self._pick(self._head(self._windows(ids, lens, 0, 0)))
+            self._prefilled = True
+            return
         out = self.model(input_ids=ids, past_key_values=self.cache,
                          position_ids=torch.arange(Smax, device=dev).unsqueeze(0), use_cache=True)
         self._pick(out.logits[torch.arange(B, device=dev), ln - 1])
@@ -483,7 +534,9 @@ class StreamSession:
         """Replace stream b by a new prompt (1-D) while the other streams keep their state: the
         prompt runs eagerly at batch 1 into a scratch StaticCache, its keys and values [:S] are copied
         into row b of every layer, and hist[b], pos[b], stop[b], limit[b], live[b] and the stream's
-        first token are written.  No recapture: the next replay reads the new state."""
+        first token are written.  No recapture: the next replay reads the new state.  With
+        prefill_chunk the prompt runs at batch 1 straight against row b of the session's cache, in
+        windows: no scratch cache, no copies."""
         from transformers.cache_utils import StaticCache
 
         if not self._prefilled:
@@ -496,6 +549,11 @@ class StreamSession:
         limit = self._limit_of(S, max_new_tokens)
         dev = self.device
         ids = prompt.to(dev).view(1, S)
+        if self.prefill_chunk is not None:
+            hidden = self._windows(ids, [S], b, 0)
+            self._set_stream(b, ids[0], 0, S, stop, limit)
+            self._pick(self._head(hidden), slice(b, b + 1))
+            return
         if self._scratch is None:
             self._scratch = StaticCache(config=self.model.config, max_cache_len=self.max_len)
         else:
@@ -512,6 +570,48 @@ class StreamSession:
         self.limit[b] = limit
         self.live[b] = 1    # before the pick, which writes live streams only and may retire this one at once
         self._pick(out.logits[:, -1], slice(b, b + 1))
+
+    def _set_stream(self, b: int, tokens: torch.Tensor, at: int, end: int, stop, limit: int) -> None:
+        """hist[b, at:end] = tokens; the stream stands at its last token, live, everything so far its prompt."""
+        self._hist_full[b, at:end] = tokens
+        self.pos[b] = end - 1
+        self.prompt_len[b] = end
+        self.stop[b] = -1 if stop is None else int(stop)
+        self.limit[b] = limit
+        self.live[b] = 1    # before the pick, which writes live streams only and may retire this one at once
+
+    @torch.inference_mode()
+    def extend(self, b: int, tokens: torch.Tensor, *, stop: Optional[int] = None,
+               max_new_tokens: Optional[int] = None) -> None:
+        """Append tokens (1-D) to stream b's sequence, live or retired -- a conversation's next turn --
+        and pick the token after them.  hist[b, pos[b]], the stream's newest token, is not in the cache
+        yet: the window is that token followed by `tokens`, at positions pos[b] .., in chunks of
+        prefill_chunk against row b of the cache.  Afterwards hist[b] holds the tokens and the stream's
+        first new token, picked from the window's last row: pos[b] stands on that token, as after
+        admit() -- it has advanced by the number of tokens and then by the pick's own step, n + 1 in
+        all -- and stop / limit / live are set as admit() sets them.  The whole sequence so far, the appended
+        tokens and the tokens generated before them included, counts as prompt from here on: the
+        presence and frequency penalties count what is generated after this call, and min_new_tokens
+        starts again.  The other streams keep their state; no recapture."""
+        if self.prefill_chunk is None:
+            raise ValueError("StreamSession.extend: open the session with prefill_chunk (the prefill attention "
+                             "places the window)")
+        if not self._prefilled:
+            raise ValueError("StreamSession.extend: prefill first (it lays the cache out)")
+        if not 0 <= b < self.batch:
+            raise ValueError(f"StreamSession.extend: stream {b} outside 0..{self.batch - 1}")
+        if tokens.dim() != 1 or tokens.numel() < 1:
+            raise ValueError("StreamSession.extend: the tokens must be 1-D and not empty")
+        p, n = int(self.pos[b]), tokens.numel()
+        if p + 1 + n >= self.max_len:
+            raise ValueError(f"StreamSession.extend: {p + 1} tokens and {n} more leave no room in max_len "
+                             f"{self.max_len}")
+        limit = self._limit_of(p + 1 + n, max_new_tokens)
+        new = tokens.to(self.device).view(n)
+        ids = torch.cat((self._hist_full[b, p:p + 1], new)).view(1, n + 1)
+        hidden = self._windows(ids, [n + 1], b, p)
+        self._set_stream(b, new, p + 1, p + 1 + n, stop, limit)
+        self._pick(self._head(hidden), slice(b, b + 1))
 
     def _step(self) -> None:
         lo = self.model(input_ids=self.tok, past_key_values=self.cache, position_ids=self._pos_ids,
@@ -601,7 +701,7 @@ class SpeculativeSession(StreamSession):
     emitted before it, so its history is the real one and the tokens stay StreamSession's."""
 
     def __init__(self, model, batch: int, max_len: int, *, draft_tokens: int = 3, ngram: int = 3, graph: bool = True,
-                 sample: bool = False):
+                 sample: bool = False, prefill_chunk: Optional[int] = None):
         from .core import MT_MAX_TOKENS
 
         if int(draft_tokens) < 1:
@@ -612,7 +712,7 @@ class SpeculativeSession(StreamSession):
         if batch * T > MT_MAX_TOKENS:
             raise ValueError(f"SpeculativeSession: batch * (draft_tokens + 1) = {batch * T} rows per step, the "
                              f"multi-token kernels take {MT_MAX_TOKENS}")
-        super().__init__(model, batch, max_len, graph=graph)
+        super().__init__(model, batch, max_len, graph=graph, prefill_chunk=prefill_chunk)
         dev = self.device
         self.T, self.ngram, self.sample = T, int(ngram), bool(sample)
         self.tok = torch.zeros((batch, T), dtype=torch.int64, device=dev)
@@ -676,13 +776,14 @@ class SpeculativeSession(StreamSession):
 
 
 def _speculative_session(model, batch: int, max_len: int, prompt_lookup_num_tokens, max_matching_ngram_size,
-                         do_sample: bool, graph: bool, who: str, sampling: bool = False) -> SpeculativeSession:
+                         do_sample: bool, graph: bool, who: str, sampling: bool = False,
+                         prefill_chunk: Optional[int] = None) -> SpeculativeSession:
     if do_sample and not sampling:
         raise ValueError(f"{who}: prompt_lookup_num_tokens verifies drafts against the greedy token; "
                          "do_sample is not supported with it unless prompt_lookup_sampling=True")
     n = PROMPT_LOOKUP_NGRAM if max_matching_ngram_size is None else int(max_matching_ngram_size)
     return SpeculativeSession(model, batch, max_len, draft_tokens=int(prompt_lookup_num_tokens), ngram=n, graph=graph,
-                              sample=bool(do_sample and sampling))
+                              sample=bool(do_sample and sampling), prefill_chunk=prefill_chunk)
 
 
 def _run_speculative(sess: SpeculativeSession, max_new_tokens: int) -> None:
@@ -732,7 +833,7 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
                     graph: bool = True, prompt_lookup_num_tokens: Optional[int] = None,
                     max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False,
                     repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
-                    no_repeat_ngram_size=None, min_new_tokens=None) -> list:
+                    no_repeat_ngram_size=None, min_new_tokens=None, prefill_chunk: Optional[int] = None) -> list:
     """generate() for prompts of different lengths: `prompts` are 1-D int64 tensors; returns one 1-D
     int64 tensor per prompt on the model's device, the prompt followed by up to max_new_tokens picked
     tokens of its own, ending with eos_token_id if the stream picked it.  A stream that stopped writes
@@ -743,7 +844,9 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     the same tokens in fewer steps wherever the text repeats itself: greedy, or with do_sample and
     prompt_lookup_sampling=True the sampled tokens of SpeculativeSession(sample=True).
     repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size, min_new_tokens:
-    as generate() takes them, one value or one per prompt."""
+    as generate() takes them, one value or one per prompt.
+    prefill_chunk: the session's (StreamSession): None keeps the whole-prompt forward, an int runs the
+    prompts through layer_ops.prefill_attention in windows of that many tokens."""
     prompts = list(prompts)
     if not prompts or any((not isinstance(p, torch.Tensor)) or p.dim() != 1 or p.numel() < 1 for p in prompts):
         raise ValueError("generate_ragged: prompts must be a non-empty sequence of non-empty 1-D tensors")
@@ -754,11 +857,11 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     if prompt_lookup_num_tokens is not None:
         sess = _speculative_session(model, B, Smax + max_new_tokens, prompt_lookup_num_tokens,
                                     max_matching_ngram_size, do_sample, graph, "generate_ragged",
-                                    prompt_lookup_sampling)
+                                    prompt_lookup_sampling, prefill_chunk)
     elif max_matching_ngram_size is not None:
         raise ValueError("generate_ragged: max_matching_ngram_size needs prompt_lookup_num_tokens")
     else:
-        sess = StreamSession(model, B, Smax + max_new_tokens, graph=graph)
+        sess = StreamSession(model, B, Smax + max_new_tokens, graph=graph, prefill_chunk=prefill_chunk)
     if do_sample:
         sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
         sess.seed(generator)

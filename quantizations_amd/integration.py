@@ -298,9 +298,40 @@ def _fused_attention_forward(mod: nn.Module, orig):
 
     `_qz_verify_pos` (int64 [B], generation.SpeculativeSession): hidden_states is [B, T, H], a window
     of T >= 2 tokens per stream at positions pos[b] .. pos[b] + T - 1, position_embeddings [B, T, D];
-    the layer runs layer_ops.decode_attention_verify -- or raises, for the same reason."""
+    the layer runs layer_ops.decode_attention_verify -- or raises, for the same reason.
+
+    `_qz_prefill` = (pos, length, row0) (generation.StreamSession(prefill_chunk=...)): hidden_states is
+    [nb, T, H], a window of up to T >= 1 prompt tokens for the nb streams of cache rows row0 .. row0 +
+    nb - 1 (a dim-0 slice of the layer's keys / values is contiguous); pos and length are int64 [nb].
+    The layer runs layer_ops.prefill_attention -- or raises.  It excludes the other two keywords."""
+    from . import layer_ops
     from .layer_ops import (decode_attention, decode_attention_streams, decode_attention_streams_supported,
                             decode_attention_supported, decode_attention_verify, decode_attention_verify_supported)
+
+    def prefill_forward(hidden_states, position_embeddings, past_key_values, spec, residual, kwargs):
+        pos, length, row0 = spec
+        layer = None
+        if (hidden_states.dim() == 3 and hidden_states.shape[1] >= 1 and position_embeddings is not None
+                and not kwargs.get("output_attentions", False) and not mod.training):
+            layer = _static_layer(past_key_values, getattr(mod, "layer_idx", None))
+        if layer is None or layer.keys.dim() != 4 or layer.keys.shape[-1] != mod.head_dim:
+            raise ValueError("_qz_prefill: a prefill window needs an initialised StaticCache layer of this "
+                             "module's head_dim")
+        nb = hidden_states.shape[0]
+        if not (isinstance(row0, int) and 0 <= row0 and row0 + nb <= layer.keys.shape[0]):
+            raise ValueError("_qz_prefill: rows row0 .. row0 + nb - 1 are not rows of the cache")
+        keys, values = layer.keys[row0:row0 + nb], layer.values[row0:row0 + nb]
+        cos, sin = position_embeddings
+        nq = keys.shape[1] * (mod.config.num_attention_heads // mod.config.num_key_value_heads)
+        if not layer_ops.prefill_attention_supported(hidden_states, cos, keys, values, pos, length, nq):
+            raise ValueError("_qz_prefill: prefill_attention does not take these shapes/dtypes/layout")
+        q = mod.q_proj(hidden_states)
+        k = mod.k_proj(hidden_states)
+        v = mod.v_proj(hidden_states)
+        if q.shape[-1] != nq * mod.head_dim or k.shape[-1] != keys.shape[1] * mod.head_dim:
+            raise ValueError("_qz_prefill: the projections' widths differ from the cache's heads")
+        out = layer_ops.prefill_attention(q, k, v, cos, sin, keys, values, pos, length, nq, mod.scaling)
+        return _project(mod.o_proj, out, residual), None
 
     def stream_forward(hidden_states, position_embeddings, past_key_values, pos, residual, kwargs):
         layer = None
@@ -343,8 +374,13 @@ def _fused_attention_forward(mod: nn.Module, orig):
         return _project(mod.o_proj, out, residual), None
 
     def forward(hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None,
-                _qz_residual=None, _qz_stream_pos=None, _qz_verify_pos=None, **kwargs):
+                _qz_residual=None, _qz_stream_pos=None, _qz_verify_pos=None, _qz_prefill=None, **kwargs):
         # _qz_residual (the residual-fused decoder layer): return residual + attention output
+        if _qz_prefill is not None:
+            if _qz_stream_pos is not None or _qz_verify_pos is not None:
+                raise ValueError("_qz_prefill excludes _qz_stream_pos and _qz_verify_pos")
+            return prefill_forward(hidden_states, position_embeddings, past_key_values, _qz_prefill, _qz_residual,
+                                   kwargs)
         if _qz_verify_pos is not None:   # taken out of kwargs, like _qz_stream_pos below
             if _qz_stream_pos is not None:
                 raise ValueError("_qz_verify_pos and _qz_stream_pos exclude each other")

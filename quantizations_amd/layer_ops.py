@@ -328,6 +328,93 @@ def decode_attention_verify(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, c
     return out
 
 
+PREFILL_TQ = 64  # query rows per workgroup of qz_prefill_attention (csrc/prefill_attn.hip: kPfTQ)
+PREFILL_TK = 64  # keys per staged tile, from absolute position 0 (kPfTK)
+
+
+def prefill_attention_supported(q: torch.Tensor, cos: torch.Tensor, key_cache: torch.Tensor,
+                                value_cache: torch.Tensor, pos, length, num_heads: int) -> bool:
+    """What qz_prefill_attention takes: T >= 1 new tokens per stream (q, or the layer input:
+    [B, T, *]), 16-bit activations, a contiguous static cache [B, Hkv, L, D] with D in {64, 128} and
+    Hq/Hkv <= 8, cos/sin [B or 1, T, D] with unit inner stride, and int64 pos / length [B],
+    contiguous, on q's device.  Metadata only: nothing is launched or allocated."""
+    if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype in (torch.float16, torch.bfloat16)
+            and q.dim() == 3 and q.shape[1] >= 1) or _needs_grad(q):
+        return False
+    if key_cache.dim() != 4 or value_cache.shape != key_cache.shape:
+        return False
+    B, Hkv, L, D = key_cache.shape
+    T = q.shape[1]
+    if (D not in (64, 128) or Hkv == 0 or num_heads % Hkv or num_heads // Hkv > 8 or q.shape[0] != B or L == 0
+            or B > 65535 or num_heads > 65535):
+        return False
+    for t in (key_cache, value_cache):
+        if t.dtype != q.dtype or t.device != q.device or not t.is_contiguous() or t.data_ptr() % 16:
+            return False
+    if not (isinstance(cos, torch.Tensor) and cos.dim() == 3 and cos.shape[0] in (1, B) and cos.shape[1] == T
+            and cos.shape[2] == D and cos.dtype == q.dtype and cos.device == q.device and cos.stride(-1) == 1):
+        return False
+    for p in (pos, length):
+        if not (isinstance(p, torch.Tensor) and p.dtype == torch.int64 and p.dim() == 1 and p.shape[0] == B
+                and p.device == q.device and p.is_contiguous()):
+            return False
+    return True
+
+
+def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                      key_cache: torch.Tensor, value_cache: torch.Tensor, pos: torch.Tensor, length: torch.Tensor,
+                      num_heads: int, scale: float) -> torch.Tensor:
+    """Causal attention of a window of T new tokens per stream against the static cache
+    (qz_prefill_attention): q [B, T, Hq*D], k/v [B, T, Hkv*D], cos/sin [B or 1, T, D], pos and length
+    int64 [B].  Token (b, i) with i < length[b] sits at position pos[b] + i: its rotated k and its v go
+    to that slot of cache row b (the bits a decode step stores there) and it sees keys 0..pos[b] + i.
+    Rows i >= length[b] write nothing and come back as zeros.  The work is O(visible keys): key tiles
+    above a query tile's last position are never loaded.  A row's bits do not depend on T, on its
+    index in the window or on the other streams, so a prompt run in chunks equals the prompt run
+    whole.  A real row past the cache end is NaN and writes nothing; pos[b] outside [0, L) makes
+    stream b's real rows NaN; pos and length are left as they are.  Returns [B, T, Hq*D]."""
+    if not prefill_attention_supported(q, cos, key_cache, value_cache, pos, length, num_heads):
+        raise ValueError("prefill_attention: unsupported shapes/dtypes/layout")
+    B, Hkv, L, D = key_cache.shape
+    T = q.shape[1]
+    if q.shape[2] != num_heads * D:
+        raise ValueError("prefill_attention: q width differs from num_heads * head_dim")
+    if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
+        raise ValueError("prefill_attention: sin must match cos")
+    if k.shape[:2] != q.shape[:2] or v.shape[:2] != q.shape[:2]:
+        raise ValueError("prefill_attention: k/v must hold q's [B, T] rows")
+    if k.shape[2] != Hkv * D or v.shape[2] != Hkv * D:
+        raise ValueError("prefill_attention: k/v width differs from the cache's heads")
+    R = B * T
+
+    def rows(t, align, mult):
+        # [B, T, W] as R rows at one stride (a multiple of `mult` elements) from an `align`-byte base
+        W = t.shape[2]
+        if t.shape[0] != B:
+            t = t.expand(B, -1, -1)
+        t = t.reshape(R, W)   # a view where the rows lie at one stride, a copy otherwise
+        if R == 1 and t.stride(-1) == 1 and t.data_ptr() % align == 0:
+            return t, W
+        if t.stride(-1) != 1 or t.stride(0) < W or t.stride(0) % mult or t.data_ptr() % align:
+            t = t.contiguous()
+        return t, t.stride(0)
+
+    q2, qs = rows(q, 16, 8)
+    k2, ks = rows(k, 2, 1)
+    v2, vs = rows(v, 4, 2)
+    c2, cs = rows(cos, 16, 8)
+    s2, ss = rows(sin, 16, 8)
+    if ss != cs:
+        s2, c2 = s2.contiguous(), c2.contiguous()
+        cs = D
+    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
+    _lib.check(_lib.lib.qz_prefill_attention(
+        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, L, q2.data_ptr(), qs, k2.data_ptr(), ks, v2.data_ptr(), vs,
+        c2.data_ptr(), s2.data_ptr(), cs, key_cache.data_ptr(), value_cache.data_ptr(), pos.data_ptr(),
+        length.data_ptr(), out.data_ptr(), num_heads * D, float(scale), _lib.stream_of(q)), "qz_prefill_attention")
+    return out
+
+
 def decode_mask(q_offset: torch.Tensor, batch: int, kv_length: int) -> torch.Tensor:
     """masking_utils.create_causal_mask's sdpa mask for one new token per sequence against a static
     cache (no padding mask, kv_offset 0): bool [batch, 1, 1, kv_length], True where kv position

@@ -400,6 +400,44 @@ int qz_prefill_attention(int dtype, int B, int T, int Hq, int Hkv, int D, int L,
                          const void *sin, long long cs_row, void *k_cache, void *v_cache, const long long *pos,
                          const long long *len, void *out, long long out_row, float scale, void *stream);
 
+/* Paged KV cache (csrc/paged_attn.hip): the three launches above through a page table.
+ *   A page holds qz_kv_page_size() = 128 positions (fixed: the decode head's key chunk, two of the
+ *   prefill kernel's key tiles).  k_pool/v_pool [P, Hkv, 128, D], contiguous, 16-B aligned, one pair
+ *   per layer; table int32 [B, NP] (device, read only, row stride table_row >= NP) serves every
+ *   layer: table[b, c] is the page of positions 128c .. 128c+127 of stream b.  Key j of stream b,
+ *   kv head h lives at ((table[b, j >> 7]*Hkv + h)*128 + (j & 127))*D; the logical cache length is
+ *   L = 128*NP.
+ *   - A row at position p sees keys 0..p, needs entries 0 .. p >> 7 and writes through entry p >> 7.
+ *   - An entry outside [0, P) is never turned into an address: a row whose write entry is invalid
+ *     writes nothing; a row with any invalid needed entry is NaN, that row only; entries above a
+ *     row's last needed page are never used as addresses, whatever they hold.
+ *   - p < 0 or p >= L: the contiguous launches' rule (NaN, nothing written).
+ *   - Two streams may name one page; the caller keeps writers out of shared pages.
+ *   - out and the pages written carry the bits of the contiguous launch on the cache gathered by the
+ *     table ([B, Hkv, 128*NP, D], L = 128*NP).
+ * qz_decode_attention_paged: qz_decode_attention_streams; grid (NP, Hq, B); work (NP > 1 only):
+ *   B*Hkv*NP*(Hq/Hkv)*(D+2) floats.  qz_decode_attention_verify_paged: qz_decode_attention_verify;
+ *   work (NP > 1 only): B*T*Hkv*NP*(Hq/Hkv)*(D+2) floats.  qz_prefill_attention_paged:
+ *   qz_prefill_attention; no workspace.  Operands, alignment rules and status codes are the contiguous
+ *   twin's with NP, P for L; in addition table null, table_row < NP, NP < 0, P < 0 or a misaligned
+ *   pool: QZ_ERR_ARG; NP = 0, P = 0 or NP > 2^24 - 1 with work to do: QZ_ERR_SHAPE. */
+int qz_kv_page_size(void);
+int qz_decode_attention_paged(int dtype, int B, int Hq, int Hkv, int D, int NP, int P, const void *q, long long q_row,
+                              const void *k, long long k_row, const void *v, long long v_row, const void *cos,
+                              const void *sin, long long cs_row, void *k_pool, void *v_pool, const int *table,
+                              long long table_row, const long long *pos, void *out, long long out_row, float *work,
+                              float scale, void *stream);
+int qz_decode_attention_verify_paged(int dtype, int B, int T, int Hq, int Hkv, int D, int NP, int P, const void *q,
+                                     long long q_row, const void *k, long long k_row, const void *v, long long v_row,
+                                     const void *cos, const void *sin, long long cs_row, void *k_pool, void *v_pool,
+                                     const int *table, long long table_row, const long long *pos, void *out,
+                                     long long out_row, float *work, float scale, void *stream);
+int qz_prefill_attention_paged(int dtype, int B, int T, int Hq, int Hkv, int D, int NP, int P, const void *q,
+                               long long q_row, const void *k, long long k_row, const void *v, long long v_row,
+                               const void *cos, const void *sin, long long cs_row, void *k_pool, void *v_pool,
+                               const int *table, long long table_row, const long long *pos, const long long *len,
+                               void *out, long long out_row, float scale, void *stream);
+
 /* Decode-step glue of the host model (transformers' LlamaModel.forward), one launch each in place
  * of the small torch kernels it issues per step.  Not part of the Linear4bit path; the
  * integration (integration.fuse_decode_glue) takes them only where they give the same values.

@@ -29,5 +29,7 @@ from .generation import (  # noqa: F401
     generate_ragged,
     prepare_for_decode,
 )
+from . import kv_pages  # noqa: F401
+from .kv_pages import KVPagePool, KVPagesExhausted  # noqa: F401
 
 __version__ = "0.1.0"

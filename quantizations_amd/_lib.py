@@ -98,6 +98,13 @@ SIGNATURES = {
                                    _ll, _p, _f, _p],
     "qz_prefill_attention": [_i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p, _p, _p,
                              _ll, _f, _p],
+    "qz_kv_page_size": [],
+    "qz_decode_attention_paged": [_i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p, _ll,
+                                  _p, _p, _ll, _p, _f, _p],
+    "qz_decode_attention_verify_paged": [_i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p,
+                                         _p, _ll, _p, _p, _ll, _p, _f, _p],
+    "qz_prefill_attention_paged": [_i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p,
+                                   _ll, _p, _p, _p, _ll, _f, _p],
     "qz_verify_step_streams": [_p, _i, _i, _i, _ll, _ll, _p, _ll, _ll, _p, _p, _p, _p, _p, _p, _p, _p],
     "qz_ngram_draft": [_i, _i, _i, _p, _ll, _ll, _p, _p, _p, _p],
     "qz_greedy_step_streams": [_p, _i, _i, _ll, _ll, _p, _ll, _ll, _p, _p, _p, _p, _p, _p, _p],

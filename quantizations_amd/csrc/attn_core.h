@@ -49,6 +49,11 @@ struct DecodeAttnArgs {
   float *part;               // nsplit > 1: [B, Hkv, nsplit, G, D + 2]
   int Hkv, G, L, nsplit;
   float scale;
+  // PAGED (paged_attn.hip): kc / vc are page pools [P, Hkv, kAttnChunk, D]; entry (b, c) of the table,
+  // at b * trow + c, names the page that holds positions kAttnChunk c .. kAttnChunk c + 127 of stream b
+  const int *table;
+  long long trow;
+  int P;
 };
 
 // The fp32 value is pinned in a register first: otherwise hipcc folds a preceding __fmul_rn
@@ -123,10 +128,16 @@ template <int D> struct AttnLds {
 // the cache already (k_verify_kv_write, the launch before), so nothing is rotated or written here
 // but q, and slot pv is read from the cache like any other key -- the bits s_kn / s_vn carry in the
 // streams kernel.  Everything after the loads is the same code again.
-template <int DT, int D, bool STREAMS = false, bool VERIFY = false>
+// PAGED (with STREAMS): the chunk's keys lie in page `page` of the pools (the caller read the table
+// entry -- uniform over the workgroup -- beside the position and checked it against [0, P)), at
+// ((page Hkv + h) kAttnChunk + (j & 127)) D: the first cache row is chosen so that every address
+// below, the new token's slot included, is the contiguous form's expression.
+template <int DT, int D, bool STREAMS = false, bool VERIFY = false, bool PAGED = false>
 __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, int split, int hq, int b,
-                                                      const AttnLds<D> &S, int cb = 0, long long pv = 0) {
+                                                      const AttnLds<D> &S, int cb = 0, long long pv = 0,
+                                                      int page = 0) {
   static_assert(STREAMS || !VERIFY, "the verify form computes its mask from the position");
+  static_assert(STREAMS || !PAGED, "the paged form has a position per stream");
   constexpr int ES = DT == QZ_DT_F32 ? 4 : 2;
   static_assert(ES == 2, "16-bit activations and caches");
   constexpr int H2 = D / 2;      // rotary half; also the share of a row one thread dots
@@ -141,7 +152,8 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
   const int G = a.G, L = a.L;
   const int h = hq / G, gq = hq - h * G;                     // kv head, query head within it
   const int j0 = split * kAttnChunk;
-  const long long crow = ((long long)(VERIFY ? cb : b) * a.Hkv + h) * L;   // first cache row of (b, h)
+  const long long crow = PAGED ? ((long long)page * a.Hkv + h) * kAttnChunk - j0   // row of key 0, were the pages in line
+                               : ((long long)(VERIFY ? cb : b) * a.Hkv + h) * L;  // first cache row of (b, h)
   const int pos_i = t & (kAttnChunk - 1), half = t >> 7;     // this thread's key position / row half
   const long long j = j0 + pos_i;
   const bool in_l = j < L;
@@ -332,5 +344,9 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
   }
   return p;
 }
+
+// k_decode_attn_combine (layer_ops.hip) over `rows` token rows, for the launches of other translation
+// units: the chunk partials of a.part into a.out.  dtype F16 / BF16, D 64 / 128 (checked by the caller).
+void launch_decode_attn_combine(int dtype, int D, const DecodeAttnArgs &a, int rows, hipStream_t s);
 
 }  // namespace qz

@@ -730,6 +730,18 @@ __global__ __launch_bounds__(256) void k_gemv_dense(const void *__restrict__ W, 
 }
 
 }  // namespace
+
+// the combine for the launches of other translation units (attn_core.h)
+void launch_decode_attn_combine(int dtype, int D, const DecodeAttnArgs &a, int rows, hipStream_t s) {
+  const dim3 g(a.Hkv, rows), b(256);
+  if (dtype == QZ_DT_F16) {
+    if (D == 64) hipLaunchKernelGGL((k_decode_attn_combine<QZ_DT_F16, 64>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_decode_attn_combine<QZ_DT_F16, 128>), g, b, 0, s, a);
+  } else {
+    if (D == 64) hipLaunchKernelGGL((k_decode_attn_combine<QZ_DT_BF16, 64>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_decode_attn_combine<QZ_DT_BF16, 128>), g, b, 0, s, a);
+  }
+}
 }  // namespace qz
 
 using namespace qz;

@@ -366,6 +366,36 @@ def _single_gpu_prepared(model, who: str) -> torch.device:
     return dev
 
 
+class PagedLayer:
+    """One layer of a PagedKVCache: the K and V page pools [P, Hkv, 128, D] as keys / values."""
+
+    def __init__(self, keys: torch.Tensor, values: torch.Tensor):
+        self.keys, self.values = keys, values
+
+
+class PagedKVCache:
+    """What a paged session hands the decoder as past_key_values: per layer one K and one V pool of
+    num_pages pages (zero-filled: a page nobody wrote yet holds finite data).  With position_ids and
+    a 4-D mask given, the decoder's forward asks nothing of it, and the fused attention reads
+    .layers[i] only; anything that tried to use it as a transformers cache ends in update()."""
+
+    def __init__(self, config, num_pages: int, dtype, device):
+        head_dim = getattr(config, "head_dim", None) or config.hidden_size // config.num_attention_heads
+        shape = (int(num_pages), config.num_key_value_heads, _ops.KV_PAGE, head_dim)
+        self.layers = [PagedLayer(torch.zeros(shape, dtype=dtype, device=device),
+                                  torch.zeros(shape, dtype=dtype, device=device))
+                       for _ in range(config.num_hidden_layers)]
+        self.bytes_per_page = 2 * len(self.layers) * shape[1] * shape[2] * shape[3] * self.layers[0].keys.element_size()
+
+    def update(self, *args, **kwargs):
+        raise RuntimeError("PagedKVCache: keys and values are written by the paged attention launches "
+                           "(_qz_paged); this forward took another path")
+
+
+def _has_adapter_bank(model) -> bool:
+    return any(m.__dict__.get("_qz_adapter_bank") is not None for m in model.modules())
+
+
 class StreamSession:
     """`batch` decode streams over `model`, each at its own position: the StaticCache
     ([B, Hkv, max_len, D] per layer) and the static buffers a captured step reads and writes -- tok
@@ -384,13 +414,33 @@ class StreamSession:
     prefill_chunk (None: everything as it was): an int c >= 1 runs prompts through
     layer_ops.prefill_attention in windows of c tokens, one model forward per window -- attention
     over the visible keys only, no [T, max_len] mask, activations sized by c, the lm_head on one row
-    per stream -- lets admit() write straight into row b of the session's cache, and opens extend()."""
+    per stream -- lets admit() write straight into row b of the session's cache, and opens extend().
 
-    def __init__(self, model, batch: int, max_len: int, *, graph: bool = True, prefill_chunk: Optional[int] = None):
+    kv_pages (None: everything as it was): an int N keeps the keys and values in N pages of 128
+    positions per layer (PagedKVCache) in place of the StaticCache, named by one page table
+    (kv_pages.KVPagePool, `self.pages`) that the three paged attention launches read on the device.
+    It needs prefill_chunk: the paged prompt path is the prefill attention.  prefill(), admit(),
+    extend() and fork() reserve a stream's pages up to its limit (plus the draft window of a
+    SpeculativeSession) before they run anything, and raise kv_pages.KVPagesExhausted with the session
+    unchanged when the pool cannot supply them, so a captured step never needs a page it does not
+    have.  release(b) retires a stream and returns its pages; fork(src, dst) continues one stream in
+    a second row for the cost of one page copy per layer.  prefix_cache=True publishes each prompt's
+    full pages and lets admit() map the resident pages of an equal prefix into the new row, running
+    the windows behind them only.  None of this recaptures: the table is a device buffer.
+    A shared page carries the bits its donor computed; a newcomer's tokens equal those of its own
+    full prefill bit for bit when the donor ran the same windows."""
+
+    def __init__(self, model, batch: int, max_len: int, *, graph: bool = True, prefill_chunk: Optional[int] = None,
+                 kv_pages: Optional[int] = None, prefix_cache: bool = False):
         if batch < 1 or max_len < 2:
             raise ValueError("StreamSession: batch must be positive and max_len at least 2")
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("StreamSession: prefill_chunk must be None or at least 1")
+        if kv_pages is not None and prefill_chunk is None:
+            raise ValueError("StreamSession: kv_pages needs prefill_chunk (the paged prompt path is the prefill "
+                             "attention)")
+        if prefix_cache and kv_pages is None:
+            raise ValueError("StreamSession: prefix_cache shares pages; open the session with kv_pages")
         self.prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
         self.device = _single_gpu_prepared(model, "StreamSession")
         from transformers.cache_utils import StaticCache
@@ -398,7 +448,15 @@ class StreamSession:
         self.model, self.batch, self.max_len = model, int(batch), int(max_len)
         self.graph = bool(graph)
         dev = self.device
-        self.cache = StaticCache(config=model.config, max_cache_len=self.max_len)
+        self.pages, self.prefix_cache, self._extra = None, bool(prefix_cache), {}
+        if kv_pages is not None:
+            from .kv_pages import KVPagePool
+
+            self.pages = KVPagePool(int(kv_pages), self.batch, -(-self.max_len // _ops.KV_PAGE), dev)
+            self.cache = PagedKVCache(model.config, int(kv_pages), model.get_input_embeddings().weight.dtype, dev)
+            self._extra = {"_qz_paged": (self.pages.table,)}
+        else:
+            self.cache = StaticCache(config=model.config, max_cache_len=self.max_len)
         self._scratch = None   # admit()'s batch-1 StaticCache, made on first use
         self.tok = torch.zeros((batch, 1), dtype=torch.int64, device=dev)
         self.pos = torch.zeros(batch, dtype=torch.int64, device=dev)
@@ -452,6 +510,8 @@ class StreamSession:
 
     def _init_cache(self) -> None:
         """Chunk mode: lay the StaticCache out before the first window (nothing calls its update())."""
+        if self.pages is not None:
+            return   # the pools are there
         cfg = self.model.config
         head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
         dtype = self.model.get_input_embeddings().weight.dtype
@@ -478,24 +538,40 @@ class StreamSession:
             # create_causal_mask hands a 4-D mask back as it is: an expanded view of one element
             h = decoder(input_ids=ids[:, s0:s0 + T], past_key_values=self.cache, position_ids=pids,
                         attention_mask=one.expand(nb, 1, T, self.max_len), use_cache=True,
-                        _qz_prefill=(pos, length, int(row0))).last_hidden_state
+                        _qz_prefill=(pos, length, int(row0)), **self._extra).last_hidden_state
             idx = n - 1 - s0
             mine = h[rows, idx.clamp(0, T - 1)]
             last = mine if last is None else torch.where(((idx >= 0) & (idx < T))[:, None], mine, last)
         return last
+
+    def _slots(self, limit: int) -> int:
+        """Cache slots a stream with this limit may write: one per position up to the limit, where a
+        retired stream of the captured batch keeps writing, and the draft window of a speculative
+        step behind it; rows past the table's end write nothing."""
+        return min(limit + getattr(self, "T", 1), self.pages.pages_per_stream * _ops.KV_PAGE)
+
+    def _salt(self, prefix_salt):
+        """The registry salt of a call, or False where sharing is off for it: K and V depend on the
+        adapter, so a model that carries an adapter bank shares only between calls that name their
+        adapter by a salt."""
+        if not self.prefix_cache or (prefix_salt is None and _has_adapter_bank(self.model)):
+            return False
+        return prefix_salt
 
     def _head(self, hidden: torch.Tensor) -> torch.Tensor:
         """lm_head on one row per stream: [nb, H] -> [nb, V]."""
         return self.model.get_output_embeddings()(hidden.unsqueeze(1))[:, 0]
 
     @torch.inference_mode()
-    def prefill(self, input_ids: torch.Tensor, lengths, *, stop=None, max_new_tokens=None) -> None:
+    def prefill(self, input_ids: torch.Tensor, lengths, *, stop=None, max_new_tokens=None, prefix_salt=None) -> None:
         """Run right-padded prompts (input_ids [B, Smax], stream b's prompt in its first lengths[b]
         columns) in one forward under the ordinary causal mask -- a real token never sees the pad to
         its right -- and pick each stream's first new token from the logits at lengths[b] - 1.  The
         pad keys left in cache slots lengths[b] .. Smax - 1 lie above pos[b]: invisible, then
         overwritten as the stream grows.  stop: a token id per stream or one for all (None / -1:
-        none); max_new_tokens likewise (None: up to max_len)."""
+        none); max_new_tokens likewise (None: up to max_len).  kv_pages: every stream's pages are
+        reserved first (KVPagesExhausted: nothing was changed), and with prefix_cache each prompt's
+        full pages are published afterwards under prefix_salt."""
         if self._prefilled:
             raise ValueError("StreamSession.prefill: a session is prefilled once; admit() replaces single streams")
         if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
@@ -509,6 +585,14 @@ class StreamSession:
             raise ValueError("StreamSession.prefill: max_new_tokens is one value or one per stream")
         limits = [self._limit_of(n, m) for n, m in zip(lens, news)]
         dev = self.device
+        if self.pages is not None:
+            try:
+                for b, lim in enumerate(limits):
+                    self.pages.reserve(b, self._slots(lim))
+            except Exception:
+                for b in range(B):
+                    self.pages.release(b)
+                raise
         ids = input_ids.to(dev)
         ln = torch.tensor(lens, device=dev)
         real = torch.arange(Smax, device=dev)[None, :] < ln[:, None]
@@ -522,6 +606,10 @@ class StreamSession:
             self._init_cache()
             self._pick(self._head(self._windows(ids, lens, 0, 0)))
             self._prefilled = True
+            salt = self._salt(prefix_salt)
+            if self.pages is not None and salt is not False:
+                for b, n in enumerate(lens):
+                    self.pages.register(b, ids[b, :n], n // _ops.KV_PAGE, salt, final_below=n)
             return
         out = self.model(input_ids=ids, past_key_values=self.cache,
                          position_ids=torch.arange(Smax, device=dev).unsqueeze(0), use_cache=True)
@@ -530,13 +618,20 @@ class StreamSession:
 
     @torch.inference_mode()
     def admit(self, b: int, prompt: torch.Tensor, *, stop: Optional[int] = None,
-              max_new_tokens: Optional[int] = None) -> None:
+              max_new_tokens: Optional[int] = None, prefix_salt=None) -> None:
         """Replace stream b by a new prompt (1-D) while the other streams keep their state: the
         prompt runs eagerly at batch 1 into a scratch StaticCache, its keys and values [:S] are copied
         into row b of every layer, and hist[b], pos[b], stop[b], limit[b], live[b] and the stream's
         first token are written.  No recapture: the next replay reads the new state.  With
         prefill_chunk the prompt runs at batch 1 straight against row b of the session's cache, in
-        windows: no scratch cache, no copies."""
+        windows: no scratch cache, no copies.
+        kv_pages: row b's pages are returned and the new stream's reserved in one step
+        (KVPagesExhausted: the session, stream b included, is as it was).  With prefix_cache the
+        prompt is looked up first: the resident pages of its longest published prefix -- at most
+        (S - 1) // 128, the last prompt token must run -- are mapped into row b and the windows start
+        behind them; the prompt's own new full pages are published afterwards.  prefix_salt keeps
+        prompts apart whose keys differ for equal tokens (streams on different adapters pass different
+        salts); with an adapter bank on the model and no salt, the call shares nothing."""
         from transformers.cache_utils import StaticCache
 
         if not self._prefilled:
@@ -550,9 +645,17 @@ class StreamSession:
         dev = self.device
         ids = prompt.to(dev).view(1, S)
         if self.prefill_chunk is not None:
-            hidden = self._windows(ids, [S], b, 0)
+            start, salt = 0, False
+            if self.pages is not None:
+                salt = self._salt(prefix_salt)
+                hit = self.pages.lookup(ids[0], salt) if salt is not False else []
+                self.pages.assign(b, hit, self._slots(limit))
+                start = _ops.KV_PAGE * len(hit)
+            hidden = self._windows(ids[:, start:], [S - start], b, start)
             self._set_stream(b, ids[0], 0, S, stop, limit)
             self._pick(self._head(hidden), slice(b, b + 1))
+            if salt is not False:
+                self.pages.register(b, ids[0], S // _ops.KV_PAGE, salt, final_below=S)
             return
         if self._scratch is None:
             self._scratch = StaticCache(config=self.model.config, max_cache_len=self.max_len)
@@ -607,15 +710,72 @@ class StreamSession:
             raise ValueError(f"StreamSession.extend: {p + 1} tokens and {n} more leave no room in max_len "
                              f"{self.max_len}")
         limit = self._limit_of(p + 1 + n, max_new_tokens)
+        if self.pages is not None:
+            self.pages.reserve(b, self._slots(limit))   # KVPagesExhausted: nothing was changed
         new = tokens.to(self.device).view(n)
         ids = torch.cat((self._hist_full[b, p:p + 1], new)).view(1, n + 1)
         hidden = self._windows(ids, [n + 1], b, p)
         self._set_stream(b, new, p + 1, p + 1 + n, stop, limit)
         self._pick(self._head(hidden), slice(b, b + 1))
 
+    def _need_pages(self, who: str) -> None:
+        if self.pages is None:
+            raise ValueError(f"StreamSession.{who}: open the session with kv_pages")
+        if not self._prefilled:
+            raise ValueError(f"StreamSession.{who}: prefill first")
+
+    @torch.inference_mode()
+    def release(self, b: int) -> None:
+        """Retire stream b and return its pages (kv_pages sessions).  The row keeps one private page
+        and stands at position 0, not live: the captured step goes on computing it on data of its
+        own, writes nothing of it to hist, and can never write into a page that was handed on."""
+        self._need_pages("release")
+        if not 0 <= b < self.batch:
+            raise ValueError(f"StreamSession.release: stream {b} outside 0..{self.batch - 1}")
+        self.pages.release(b)
+        self.live[b] = 0
+        self.pos[b] = 0
+        if hasattr(self, "_draft"):
+            self._draft()   # a speculative session's position ids follow pos
+
+    @torch.inference_mode()
+    def fork(self, src: int, dst: int, *, stop: Optional[int] = None, max_new_tokens: Optional[int] = None) -> None:
+        """Continue stream src in row dst as well (kv_pages sessions): dst is released, then names
+        src's pages below pos[src] >> 7 -- final, since src only writes at its position and above --
+        gets a copy of the partial page behind them (every layer, K and V) and src's hist row, tok, pos
+        and prompt_len.  It keeps its own sampling parameters, penalties and uniform row: several
+        samples of one prompt for one prefill.  stop / max_new_tokens: None takes src's stop token /
+        src's limit and liveness.  KVPagesExhausted: the session, row dst included, is as it was."""
+        self._need_pages("fork")
+        if not (0 <= src < self.batch and 0 <= dst < self.batch) or src == dst:
+            raise ValueError(f"StreamSession.fork: two different streams of 0..{self.batch - 1}")
+        p = int(self.pos[src])
+        limit = int(self.limit[src]) if max_new_tokens is None else self._limit_of(p + 1, max_new_tokens)
+        pair = self.pages.fork(src, dst, p, self._slots(limit))
+        if pair is not None:
+            for layer in self.cache.layers:
+                layer.keys[pair[1]].copy_(layer.keys[pair[0]])
+                layer.values[pair[1]].copy_(layer.values[pair[0]])
+        self._hist_full[dst].copy_(self._hist_full[src])
+        self.tok[dst].copy_(self.tok[src])
+        if hasattr(self, "pos_ids"):
+            self.pos_ids[dst].copy_(self.pos_ids[src])
+        self.pos[dst] = p
+        self.prompt_len[dst] = self.prompt_len[src]
+        self.stop[dst] = self.stop[src] if stop is None else int(stop)
+        self.limit[dst] = limit
+        self.live[dst] = self.live[src] if max_new_tokens is None else 1
+
+    def page_stats(self) -> dict:
+        """The pool's pages by state -- free, held (named by a stream), idle (published, named by
+        nobody, evictable) and total -- and the bytes one page takes over all layers, K and V."""
+        if self.pages is None:
+            raise ValueError("StreamSession.page_stats: open the session with kv_pages")
+        return dict(self.pages.stats(), bytes_per_page=self.cache.bytes_per_page)
+
     def _step(self) -> None:
         lo = self.model(input_ids=self.tok, past_key_values=self.cache, position_ids=self._pos_ids,
-                        attention_mask=self._mask, use_cache=True, _qz_stream_pos=self.pos).logits
+                        attention_mask=self._mask, use_cache=True, _qz_stream_pos=self.pos, **self._extra).logits
         self._pick(lo[:, -1])
 
     def _step_state(self) -> list:
@@ -701,7 +861,8 @@ class SpeculativeSession(StreamSession):
     emitted before it, so its history is the real one and the tokens stay StreamSession's."""
 
     def __init__(self, model, batch: int, max_len: int, *, draft_tokens: int = 3, ngram: int = 3, graph: bool = True,
-                 sample: bool = False, prefill_chunk: Optional[int] = None):
+                 sample: bool = False, prefill_chunk: Optional[int] = None, kv_pages: Optional[int] = None,
+                 prefix_cache: bool = False):
         from .core import MT_MAX_TOKENS
 
         if int(draft_tokens) < 1:
@@ -712,7 +873,8 @@ class SpeculativeSession(StreamSession):
         if batch * T > MT_MAX_TOKENS:
             raise ValueError(f"SpeculativeSession: batch * (draft_tokens + 1) = {batch * T} rows per step, the "
                              f"multi-token kernels take {MT_MAX_TOKENS}")
-        super().__init__(model, batch, max_len, graph=graph, prefill_chunk=prefill_chunk)
+        super().__init__(model, batch, max_len, graph=graph, prefill_chunk=prefill_chunk, kv_pages=kv_pages,
+                         prefix_cache=prefix_cache)
         dev = self.device
         self.T, self.ngram, self.sample = T, int(ngram), bool(sample)
         self.tok = torch.zeros((batch, T), dtype=torch.int64, device=dev)
@@ -752,7 +914,7 @@ class SpeculativeSession(StreamSession):
 
     def _step(self) -> None:
         lo = self.model(input_ids=self.tok, past_key_values=self.cache, position_ids=self.pos_ids,
-                        attention_mask=self._mask, use_cache=True, _qz_verify_pos=self.pos).logits
+                        attention_mask=self._mask, use_cache=True, _qz_verify_pos=self.pos, **self._extra).logits
         lo = lo.reshape(self.batch * self.T, -1)
         self._process(lo, tok=self.tok)    # row i sees the drafts 1..i it was fed after
         if self._greedy_only:
@@ -777,13 +939,13 @@ class SpeculativeSession(StreamSession):
 
 def _speculative_session(model, batch: int, max_len: int, prompt_lookup_num_tokens, max_matching_ngram_size,
                          do_sample: bool, graph: bool, who: str, sampling: bool = False,
-                         prefill_chunk: Optional[int] = None) -> SpeculativeSession:
+                         prefill_chunk: Optional[int] = None, kv_pages: Optional[int] = None) -> SpeculativeSession:
     if do_sample and not sampling:
         raise ValueError(f"{who}: prompt_lookup_num_tokens verifies drafts against the greedy token; "
                          "do_sample is not supported with it unless prompt_lookup_sampling=True")
     n = PROMPT_LOOKUP_NGRAM if max_matching_ngram_size is None else int(max_matching_ngram_size)
     return SpeculativeSession(model, batch, max_len, draft_tokens=int(prompt_lookup_num_tokens), ngram=n, graph=graph,
-                              sample=bool(do_sample and sampling), prefill_chunk=prefill_chunk)
+                              sample=bool(do_sample and sampling), prefill_chunk=prefill_chunk, kv_pages=kv_pages)
 
 
 def _run_speculative(sess: SpeculativeSession, max_new_tokens: int) -> None:
@@ -833,7 +995,8 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
                     graph: bool = True, prompt_lookup_num_tokens: Optional[int] = None,
                     max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False,
                     repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
-                    no_repeat_ngram_size=None, min_new_tokens=None, prefill_chunk: Optional[int] = None) -> list:
+                    no_repeat_ngram_size=None, min_new_tokens=None, prefill_chunk: Optional[int] = None,
+                    kv_pages: Optional[int] = None) -> list:
     """generate() for prompts of different lengths: `prompts` are 1-D int64 tensors; returns one 1-D
     int64 tensor per prompt on the model's device, the prompt followed by up to max_new_tokens picked
     tokens of its own, ending with eos_token_id if the stream picked it.  A stream that stopped writes
@@ -846,7 +1009,9 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size, min_new_tokens:
     as generate() takes them, one value or one per prompt.
     prefill_chunk: the session's (StreamSession): None keeps the whole-prompt forward, an int runs the
-    prompts through layer_ops.prefill_attention in windows of that many tokens."""
+    prompts through layer_ops.prefill_attention in windows of that many tokens.
+    kv_pages: the session's: that many pages of 128 positions per layer in place of a cache row of
+    Smax + max_new_tokens positions per prompt (needs prefill_chunk)."""
     prompts = list(prompts)
     if not prompts or any((not isinstance(p, torch.Tensor)) or p.dim() != 1 or p.numel() < 1 for p in prompts):
         raise ValueError("generate_ragged: prompts must be a non-empty sequence of non-empty 1-D tensors")
@@ -857,11 +1022,12 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     if prompt_lookup_num_tokens is not None:
         sess = _speculative_session(model, B, Smax + max_new_tokens, prompt_lookup_num_tokens,
                                     max_matching_ngram_size, do_sample, graph, "generate_ragged",
-                                    prompt_lookup_sampling, prefill_chunk)
+                                    prompt_lookup_sampling, prefill_chunk, kv_pages)
     elif max_matching_ngram_size is not None:
         raise ValueError("generate_ragged: max_matching_ngram_size needs prompt_lookup_num_tokens")
     else:
-        sess = StreamSession(model, B, Smax + max_new_tokens, graph=graph, prefill_chunk=prefill_chunk)
+        sess = StreamSession(model, B, Smax + max_new_tokens, graph=graph, prefill_chunk=prefill_chunk,
+                             kv_pages=kv_pages)
     if do_sample:
         sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
         sess.seed(generator)

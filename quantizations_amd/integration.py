@@ -303,10 +303,58 @@ def _fused_attention_forward(mod: nn.Module, orig):
     `_qz_prefill` = (pos, length, row0) (generation.StreamSession(prefill_chunk=...)): hidden_states is
     [nb, T, H], a window of up to T >= 1 prompt tokens for the nb streams of cache rows row0 .. row0 +
     nb - 1 (a dim-0 slice of the layer's keys / values is contiguous); pos and length are int64 [nb].
-    The layer runs layer_ops.prefill_attention -- or raises.  It excludes the other two keywords."""
+    The layer runs layer_ops.prefill_attention -- or raises.  It excludes the other two keywords.
+
+    `_qz_paged` = (table,) (generation.StreamSession(kv_pages=...)) goes beside one of the three
+    keywords above: the cache's layer holds page pools [P, Hkv, 128, D] as keys / values (generation.
+    PagedKVCache) and table is the int32 [B, NP] page table all layers share.  The layer runs the
+    paged twin of that keyword's launch (layer_ops.decode_attention_paged, decode_attention_verify_paged,
+    prefill_attention_paged; a prefill window's streams are rows row0 .. row0 + nb - 1 of the table)
+    -- or raises."""
     from . import layer_ops
     from .layer_ops import (decode_attention, decode_attention_streams, decode_attention_streams_supported,
                             decode_attention_supported, decode_attention_verify, decode_attention_verify_supported)
+
+    def paged_forward(hidden_states, position_embeddings, past_key_values, paged, stream_pos, verify_pos, prefill,
+                      residual, kwargs):
+        if (stream_pos is not None) + (verify_pos is not None) + (prefill is not None) != 1:
+            raise ValueError("_qz_paged goes with exactly one of _qz_stream_pos, _qz_verify_pos and _qz_prefill")
+        layers, idx = getattr(past_key_values, "layers", None), getattr(mod, "layer_idx", None)
+        layer = layers[idx] if layers is not None and idx is not None and idx < len(layers) else None
+        if (layer is None or type(layer).__name__ != "PagedLayer" or hidden_states.dim() != 3
+                or position_embeddings is None or kwargs.get("output_attentions", False) or mod.training
+                or layer.keys.dim() != 4 or layer.keys.shape[-1] != mod.head_dim):
+            raise ValueError("_qz_paged: the paged launches need a PagedKVCache layer of this module's head_dim")
+        table, = paged
+        keys, values = layer.keys, layer.values
+        cos, sin = position_embeddings
+        nq = keys.shape[1] * (mod.config.num_attention_heads // mod.config.num_key_value_heads)
+        if prefill is not None:
+            pos, length, row0 = prefill
+            nb = hidden_states.shape[0]
+            if not (isinstance(row0, int) and 0 <= row0 and row0 + nb <= table.shape[0]):
+                raise ValueError("_qz_paged: rows row0 .. row0 + nb - 1 are not rows of the table")
+            table = table[row0:row0 + nb]
+            ok = layer_ops.prefill_attention_paged_supported(hidden_states, cos, keys, values, table, pos, length, nq)
+        elif verify_pos is not None:
+            ok = layer_ops.decode_attention_verify_paged_supported(hidden_states, cos, keys, values, table, verify_pos, nq)
+        else:
+            ok = layer_ops.decode_attention_paged_supported(hidden_states, cos, keys, values, table, stream_pos, nq)
+        if not ok:
+            raise ValueError("_qz_paged: the paged launch does not take these shapes/dtypes/layout")
+        q = mod.q_proj(hidden_states)
+        k = mod.k_proj(hidden_states)
+        v = mod.v_proj(hidden_states)
+        if q.shape[-1] != nq * mod.head_dim or k.shape[-1] != keys.shape[1] * mod.head_dim:
+            raise ValueError("_qz_paged: the projections' widths differ from the pools' heads")
+        if prefill is not None:
+            out = layer_ops.prefill_attention_paged(q, k, v, cos, sin, keys, values, table, pos, length, nq, mod.scaling)
+        elif verify_pos is not None:
+            out = layer_ops.decode_attention_verify_paged(q, k, v, cos, sin, keys, values, table, verify_pos, nq,
+                                                          mod.scaling)
+        else:
+            out = layer_ops.decode_attention_paged(q, k, v, cos, sin, keys, values, table, stream_pos, nq, mod.scaling)
+        return _project(mod.o_proj, out, residual), None
 
     def prefill_forward(hidden_states, position_embeddings, past_key_values, spec, residual, kwargs):
         pos, length, row0 = spec
@@ -374,8 +422,12 @@ def _fused_attention_forward(mod: nn.Module, orig):
         return _project(mod.o_proj, out, residual), None
 
     def forward(hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None,
-                _qz_residual=None, _qz_stream_pos=None, _qz_verify_pos=None, _qz_prefill=None, **kwargs):
+                _qz_residual=None, _qz_stream_pos=None, _qz_verify_pos=None, _qz_prefill=None, _qz_paged=None,
+                **kwargs):
         # _qz_residual (the residual-fused decoder layer): return residual + attention output
+        if _qz_paged is not None:
+            return paged_forward(hidden_states, position_embeddings, past_key_values, _qz_paged, _qz_stream_pos,
+                                 _qz_verify_pos, _qz_prefill, _qz_residual, kwargs)
         if _qz_prefill is not None:
             if _qz_stream_pos is not None or _qz_verify_pos is not None:
                 raise ValueError("_qz_prefill excludes _qz_stream_pos and _qz_verify_pos")

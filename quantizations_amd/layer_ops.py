@@ -415,6 +415,185 @@ def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: to
     return out
 
 
+KV_PAGE = 128  # positions per page of the paged cache (qz_kv_page_size(): the decode head's key chunk)
+
+
+def _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads: int, min_t: int, cos_batches) -> bool:
+    """What the three paged launches ask of the activations, the pools [P, Hkv, 128, D], the table
+    int32 [B, NP] with unit inner stride, pos int64 [B] and cos/sin [*, T, D]."""
+    if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype in (torch.float16, torch.bfloat16)
+            and q.dim() == 3 and q.shape[1] >= min_t) or _needs_grad(q):
+        return False
+    if not (isinstance(k_pool, torch.Tensor) and isinstance(v_pool, torch.Tensor) and k_pool.dim() == 4
+            and v_pool.shape == k_pool.shape and k_pool.shape[2] == KV_PAGE):
+        return False
+    P, Hkv, _, D = k_pool.shape
+    B, T = q.shape[0], q.shape[1]
+    if (D not in (64, 128) or Hkv == 0 or P == 0 or num_heads % Hkv or num_heads // Hkv > 8 or B > 65535
+            or num_heads > 65535):
+        return False
+    for t in (k_pool, v_pool):
+        if t.dtype != q.dtype or t.device != q.device or not t.is_contiguous() or t.data_ptr() % 16:
+            return False
+    if not (isinstance(table, torch.Tensor) and table.dtype == torch.int32 and table.dim() == 2
+            and table.shape[0] == B and table.shape[1] >= 1 and table.device == q.device
+            and table.stride(1) == 1 and table.stride(0) >= table.shape[1]):
+        return False
+    if not (isinstance(cos, torch.Tensor) and cos.dim() == 3 and cos.shape[0] in cos_batches(B) and cos.shape[1] == T
+            and cos.shape[2] == D and cos.dtype == q.dtype and cos.device == q.device and cos.stride(-1) == 1):
+        return False
+    return (isinstance(pos, torch.Tensor) and pos.dtype == torch.int64 and pos.dim() == 1 and pos.shape[0] == B
+            and pos.device == q.device and pos.is_contiguous())
+
+
+def decode_attention_paged_supported(q: torch.Tensor, cos: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                                     table, pos, num_heads: int) -> bool:
+    """What qz_decode_attention_paged takes: one new token per stream (q [B, 1, *]), 16-bit
+    activations, pools [P, Hkv, 128, D] with D in {64, 128} and Hq/Hkv <= 8, a table int32 [B, NP] with
+    unit inner stride, cos/sin [B or 1, 1, D] and pos int64 [B], all on q's device.  Metadata only:
+    nothing is launched or allocated."""
+    return (isinstance(q, torch.Tensor) and q.dim() == 3 and q.shape[1] == 1
+            and _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 1, lambda B: (1, B)))
+
+
+def decode_attention_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                           k_pool: torch.Tensor, v_pool: torch.Tensor, table: torch.Tensor, pos: torch.Tensor,
+                           num_heads: int, scale: float) -> torch.Tensor:
+    """decode_attention_streams through a page table (qz_decode_attention_paged): pools
+    [P, Hkv, 128, D], table int32 [B, NP]; key j of stream b lives in page table[b, j >> 7] at slot
+    j & 127, and the logical cache length is 128 NP.  Output and the slot written carry the bits of
+    decode_attention_streams on the cache the table gathers.  A table entry outside [0, P) that the
+    stream needs makes its row NaN and is never dereferenced; entries above pos[b] >> 7 may hold
+    anything.  Returns [B, 1, Hq*D]."""
+    if not decode_attention_paged_supported(q, cos, k_pool, v_pool, table, pos, num_heads):
+        raise ValueError("decode_attention_paged: unsupported shapes/dtypes/layout")
+    P, Hkv, _, D = k_pool.shape
+    B, NP = table.shape
+    # _attention_launch_operands reads only the shape of its cache operand: [B, Hkv, L, D]
+    shape = k_pool.as_strided((B, Hkv, NP * KV_PAGE, D), (0, 0, 0, 0))
+    q2, k2, v2, out, work, cs_row = _attention_launch_operands("decode_attention_paged", q, k, v, cos, sin, shape,
+                                                               num_heads)
+    _lib.check(_lib.lib.qz_decode_attention_paged(
+        _lib.dtype_code(q.dtype), B, num_heads, Hkv, D, NP, P, q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0),
+        v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cs_row, k_pool.data_ptr(), v_pool.data_ptr(),
+        table.data_ptr(), table.stride(0), pos.data_ptr(), out.data_ptr(), num_heads * D,
+        work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)), "qz_decode_attention_paged")
+    return out
+
+
+def decode_attention_verify_paged_supported(q: torch.Tensor, cos: torch.Tensor, k_pool: torch.Tensor,
+                                            v_pool: torch.Tensor, table, pos, num_heads: int) -> bool:
+    """What qz_decode_attention_verify_paged takes: T >= 2 new tokens per stream (q [B, T, *]),
+    decode_attention_paged_supported's pools, table and pos, and cos/sin [B, T, D] whose B T rows lie
+    at one stride.  Metadata only: nothing is launched or allocated."""
+    if not _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 2, lambda B: (B,)):
+        return False
+    B, T = q.shape[0], q.shape[1]
+    return B * T <= 65535 and (B == 1 or cos.stride(0) == T * cos.stride(1))
+
+
+def decode_attention_verify_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor,
+                                  sin: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, table: torch.Tensor,
+                                  pos: torch.Tensor, num_heads: int, scale: float) -> torch.Tensor:
+    """decode_attention_verify through a page table (qz_decode_attention_verify_paged): token (b, i)
+    sits at position pos[b] + i, writes through table[b, (pos[b] + i) >> 7] and sees keys
+    0..pos[b] + i.  Bits are decode_attention_verify's on the gathered cache; a row that needs an
+    entry outside [0, P) is NaN and a row whose write entry is invalid writes nothing.  Returns
+    [B, T, Hq*D]."""
+    if not decode_attention_verify_paged_supported(q, cos, k_pool, v_pool, table, pos, num_heads):
+        raise ValueError("decode_attention_verify_paged: unsupported shapes/dtypes/layout")
+    P, Hkv, _, D = k_pool.shape
+    B, NP = table.shape
+    T, G = q.shape[1], num_heads // Hkv
+    if q.shape[2] != num_heads * D:
+        raise ValueError("decode_attention_verify_paged: q width differs from num_heads * head_dim")
+    if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
+        raise ValueError("decode_attention_verify_paged: sin must match cos")
+    if k.shape[:2] != q.shape[:2] or v.shape[:2] != q.shape[:2]:
+        raise ValueError("decode_attention_verify_paged: k/v must hold q's [B, T] rows")
+    R = B * T
+    q2, k2, v2 = (t.reshape(R, -1) for t in (q, k, v))
+    k2 = k2 if k2.stride(-1) == 1 else k2.contiguous()
+    q2 = q2 if q2.stride(-1) == 1 else q2.contiguous()
+    if v2.stride(-1) != 1 or v2.stride(0) % 2 or v2.data_ptr() % 4:
+        v2 = v2.contiguous()
+    if k2.shape[1] != Hkv * D or v2.shape[1] != Hkv * D:
+        raise ValueError("decode_attention_verify_paged: k/v width differs from the pools' heads")
+    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
+    work = torch.empty(R * Hkv * NP * G * (D + 2), dtype=torch.float32, device=q.device) if NP > 1 else None
+    _lib.check(_lib.lib.qz_decode_attention_verify_paged(
+        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, NP, P, q2.data_ptr(), q2.stride(0), k2.data_ptr(),
+        k2.stride(0), v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cos.stride(1), k_pool.data_ptr(),
+        v_pool.data_ptr(), table.data_ptr(), table.stride(0), pos.data_ptr(), out.data_ptr(), num_heads * D,
+        work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)),
+        "qz_decode_attention_verify_paged")
+    return out
+
+
+def prefill_attention_paged_supported(q: torch.Tensor, cos: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                                      table, pos, length, num_heads: int) -> bool:
+    """What qz_prefill_attention_paged takes: T >= 1 new tokens per stream (q [B, T, *]),
+    decode_attention_paged_supported's pools, table and pos, cos/sin [B or 1, T, D] with unit inner
+    stride and an int64 length [B].  Metadata only: nothing is launched or allocated."""
+    if not _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 1, lambda B: (1, B)):
+        return False
+    return (isinstance(length, torch.Tensor) and length.dtype == torch.int64 and length.dim() == 1
+            and length.shape[0] == q.shape[0] and length.device == q.device and length.is_contiguous())
+
+
+def prefill_attention_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                            k_pool: torch.Tensor, v_pool: torch.Tensor, table: torch.Tensor, pos: torch.Tensor,
+                            length: torch.Tensor, num_heads: int, scale: float) -> torch.Tensor:
+    """prefill_attention through a page table (qz_prefill_attention_paged): token (b, i) with
+    i < length[b] sits at position pos[b] + i, writes through table[b, (pos[b] + i) >> 7] and sees keys
+    0..pos[b] + i; a 64-key tile's base comes from table[b, tile >> 1].  Bits are prefill_attention's
+    on the gathered cache, so a window split into several calls equals the whole window.  A row that
+    needs an entry outside [0, P) is NaN; a row whose write entry is invalid writes nothing.  Returns
+    [B, T, Hq*D]."""
+    if not prefill_attention_paged_supported(q, cos, k_pool, v_pool, table, pos, length, num_heads):
+        raise ValueError("prefill_attention_paged: unsupported shapes/dtypes/layout")
+    P, Hkv, _, D = k_pool.shape
+    B, NP = table.shape
+    T = q.shape[1]
+    if q.shape[2] != num_heads * D:
+        raise ValueError("prefill_attention_paged: q width differs from num_heads * head_dim")
+    if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
+        raise ValueError("prefill_attention_paged: sin must match cos")
+    if k.shape[:2] != q.shape[:2] or v.shape[:2] != q.shape[:2]:
+        raise ValueError("prefill_attention_paged: k/v must hold q's [B, T] rows")
+    if k.shape[2] != Hkv * D or v.shape[2] != Hkv * D:
+        raise ValueError("prefill_attention_paged: k/v width differs from the pools' heads")
+    q2, qs = _token_rows(q, B, T, 16, 8)
+    k2, ks = _token_rows(k, B, T, 2, 1)
+    v2, vs = _token_rows(v, B, T, 4, 2)
+    c2, cs = _token_rows(cos, B, T, 16, 8)
+    s2, ss = _token_rows(sin, B, T, 16, 8)
+    if ss != cs:
+        s2, c2 = s2.contiguous(), c2.contiguous()
+        cs = D
+    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
+    _lib.check(_lib.lib.qz_prefill_attention_paged(
+        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, NP, P, q2.data_ptr(), qs, k2.data_ptr(), ks, v2.data_ptr(),
+        vs, c2.data_ptr(), s2.data_ptr(), cs, k_pool.data_ptr(), v_pool.data_ptr(), table.data_ptr(), table.stride(0),
+        pos.data_ptr(), length.data_ptr(), out.data_ptr(), num_heads * D, float(scale), _lib.stream_of(q)),
+        "qz_prefill_attention_paged")
+    return out
+
+
+def _token_rows(t: torch.Tensor, B: int, T: int, align: int, mult: int):
+    """[B or 1, T, W] as B T rows at one stride (a multiple of `mult` elements) from an `align`-byte
+    base: prefill_attention's row-view rule.  Returns (tensor, row stride)."""
+    W = t.shape[2]
+    if t.shape[0] != B:
+        t = t.expand(B, -1, -1)
+    t = t.reshape(B * T, W)   # a view where the rows lie at one stride, a copy otherwise
+    if B * T == 1 and t.stride(-1) == 1 and t.data_ptr() % align == 0:
+        return t, W
+    if t.stride(-1) != 1 or t.stride(0) < W or t.stride(0) % mult or t.data_ptr() % align:
+        t = t.contiguous()
+    return t, t.stride(0)
+
+
 def decode_mask(q_offset: torch.Tensor, batch: int, kv_length: int) -> torch.Tensor:
     """masking_utils.create_causal_mask's sdpa mask for one new token per sequence against a static
     cache (no padding mask, kv_offset 0): bool [batch, 1, 1, kv_length], True where kv position

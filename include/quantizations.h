@@ -438,6 +438,39 @@ int qz_prefill_attention_paged(int dtype, int B, int T, int Hq, int Hkv, int D, 
                                const int *table, long long table_row, const long long *pos, const long long *len,
                                void *out, long long out_row, float scale, void *stream);
 
+/* FP8 paged KV cache, "kv8" (csrc/paged_attn_kv8.hip): the three paged launches over byte pools.
+ *   A cache row (one position of one kv head, D elements of K or of V) is D OCP E4M3 codes and one
+ *   scale byte s = e + 127 that stands for 2^e: e is the smallest exponent with absmax*2^-e <= 448,
+ *   not below e_min (-15 for fp16, -124 for bf16); code i is x_i*2^-e rounded to nearest even.  A row
+ *   holding an inf or a NaN has s = 255 and every code 0x7F.  A value reads back as decode(code)*2^e
+ *   rounded to nearest even into the storage dtype (exact for every row the writer produces, but for
+ *   fp16 elements above 63488, which return as inf), NaN where s = 255 or the code is 0x7F / 0xFF; a
+ *   zero-filled page reads as zeros.
+ *   k_pool/v_pool uint8 [P, Hkv, 128*(D+1)], contiguous, 16-B aligned: the block of (page, kv head),
+ *   qz_kv8_page_head_bytes(D) = 128*(D+1) bytes (D = 64 / 128; QZ_ERR_SHAPE otherwise), holds the
+ *   128*D codes as [128, D], then the 128 scale bytes.
+ *   Operands (dtype is the activations': fp16 / bf16), the table, validity rules, workspaces,
+ *   alignment rules and status codes are the _paged twins'.  K is quantised after the rotary; the
+ *   decode launch scores the new token's DEQUANTISED rows, so out carries the bits of the _paged
+ *   launch with identity cos/sin on the dequantised pools, the rotated q and the dequantised new rows. */
+int qz_kv8_page_head_bytes(int D);
+int qz_decode_attention_paged_kv8(int dtype, int B, int Hq, int Hkv, int D, int NP, int P, const void *q,
+                                  long long q_row, const void *k, long long k_row, const void *v, long long v_row,
+                                  const void *cos, const void *sin, long long cs_row, void *k_pool, void *v_pool,
+                                  const int *table, long long table_row, const long long *pos, void *out,
+                                  long long out_row, float *work, float scale, void *stream);
+int qz_decode_attention_verify_paged_kv8(int dtype, int B, int T, int Hq, int Hkv, int D, int NP, int P, const void *q,
+                                         long long q_row, const void *k, long long k_row, const void *v,
+                                         long long v_row, const void *cos, const void *sin, long long cs_row,
+                                         void *k_pool, void *v_pool, const int *table, long long table_row,
+                                         const long long *pos, void *out, long long out_row, float *work,
+                                         float scale, void *stream);
+int qz_prefill_attention_paged_kv8(int dtype, int B, int T, int Hq, int Hkv, int D, int NP, int P, const void *q,
+                                   long long q_row, const void *k, long long k_row, const void *v, long long v_row,
+                                   const void *cos, const void *sin, long long cs_row, void *k_pool, void *v_pool,
+                                   const int *table, long long table_row, const long long *pos, const long long *len,
+                                   void *out, long long out_row, float scale, void *stream);
+
 /* Decode-step glue of the host model (transformers' LlamaModel.forward), one launch each in place
  * of the small torch kernels it issues per step.  Not part of the Linear4bit path; the
  * integration (integration.fuse_decode_glue) takes them only where they give the same values.

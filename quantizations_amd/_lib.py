@@ -105,6 +105,13 @@ SIGNATURES = {
                                          _p, _ll, _p, _p, _ll, _p, _f, _p],
     "qz_prefill_attention_paged": [_i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p,
                                    _ll, _p, _p, _p, _ll, _f, _p],
+    "qz_kv8_page_head_bytes": [_i],
+    "qz_decode_attention_paged_kv8": [_i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p,
+                                      _ll, _p, _p, _ll, _p, _f, _p],
+    "qz_decode_attention_verify_paged_kv8": [_i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p,
+                                             _p, _p, _ll, _p, _p, _ll, _p, _f, _p],
+    "qz_prefill_attention_paged_kv8": [_i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p,
+                                       _p, _ll, _p, _p, _p, _ll, _f, _p],
     "qz_verify_step_streams": [_p, _i, _i, _i, _ll, _ll, _p, _ll, _ll, _p, _p, _p, _p, _p, _p, _p, _p],
     "qz_ngram_draft": [_i, _i, _i, _p, _ll, _ll, _p, _p, _p, _p],
     "qz_greedy_step_streams": [_p, _i, _i, _ll, _ll, _p, _ll, _ll, _p, _p, _p, _p, _p, _p, _p],

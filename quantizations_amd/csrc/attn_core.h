@@ -86,6 +86,95 @@ template <int DT> __device__ __forceinline__ float dot2_dt(uint32_t a, uint32_t 
     return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(b16x2, a), __builtin_bit_cast(b16x2, b), c, false);
 }
 
+// ---- kv8: FP8 cache rows (paged_attn_kv8.hip).  A row of D 16-bit values is D OCP E4M3 codes and one
+// scale byte s = e + 127 that stands for 2^e (s = 255: a non-finite row, every value NaN).  The scale is
+// a power of two, so decode(code) * 2^e is a 16-bit value exactly and "convert at the load" leaves the
+// bits of the 16-bit launch on the dequantised cache (DESIGN, "FP8 paged KV cache").
+// The block of (page, kv head) is kAttnChunk * D code bytes, then kAttnChunk scale bytes.
+template <int D> struct Kv8 {
+  static constexpr int kBlock = kAttnChunk * (D + 1);   // bytes of one (page, kv head)
+  static constexpr int kScales = kAttnChunk * D;        // offset of the scale bytes in a block
+};
+template <int DT> constexpr int kKv8Emin = DT == QZ_DT_F16 ? -15 : -124;
+
+// the scale byte of a row from the largest |x| of the row as fp32 bits (sign cleared; compared as
+// unsigned, so inf and NaN win): the smallest e with a * 2^-e <= 448 = 1.75 * 2^8, not below e_min
+template <int DT> __device__ __forceinline__ uint32_t kv8_scale_byte(uint32_t amax) {
+  const int E = (int)(amax >> 23);
+  if (E == 255) return 255u;
+  const int e = E - 127 - 8 + ((amax & 0x7FFFFFu) > 0x600000u ? 1 : 0);
+  return (uint32_t)(max(e, kKv8Emin<DT>) + 127);
+}
+// two values -> two codes, (a) | (b) << 8: an exact scaling, then the hardware's RNE conversion (the
+// scaled magnitude is at most 448: the overflow mode never matters)
+__device__ __forceinline__ uint32_t kv8_quant2(float a, float b, uint32_t s) {
+  if (s == 255u) return 0x7F7Fu;
+  const int e = 127 - (int)s;
+  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(__builtin_ldexpf(a, e), __builtin_ldexpf(b, e), 0, false) & 0xFFFFu;
+}
+template <int DT> constexpr uint32_t kKv8Nan2 = DT == QZ_DT_F16 ? 0x7E007E00u : 0x7FC07FC0u;
+// 2^(s - 127) as an fp32 (s = 0: the subnormal 2^-127; s != 255)
+__device__ __forceinline__ float kv8_scale_f32(uint32_t s) { return __uint_as_float(s == 0u ? 0x00400000u : s << 23); }
+// codes 2 HI, 2 HI + 1 of a word -> a packed pair of storage-dtype values: decode(code) * sc in one
+// instruction, v_cvt_scalef32_pk_{f16,bf16}_fp8.  tests/test_gpu_kv8_attention.py reads every code at every
+// legal scale byte back through it: it is decode * 2^e rounded to nearest even, subnormal results and
+// the overflow to inf at the top scale included -- the bits of v_cvt_pk_f32_fp8, v_ldexp_f32 and the
+// packed RNE conversion, which passed the same test before it.
+template <int DT, bool HI> __device__ __forceinline__ uint32_t kv8_dq2(uint32_t codes, float sc) {
+  if constexpr (DT == QZ_DT_F16) return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)codes, sc, HI));
+  else return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)codes, sc, HI));
+}
+// 16 codes -> 8 words
+template <int DT> __device__ __forceinline__ void kv8_dq16(const u32x4 c, uint32_t s, uint32_t *w) {
+  const float sc = kv8_scale_f32(s);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    w[2 * q] = s == 255u ? kKv8Nan2<DT> : kv8_dq2<DT, false>(c[q], sc);
+    w[2 * q + 1] = s == 255u ? kKv8Nan2<DT> : kv8_dq2<DT, true>(c[q], sc);
+  }
+}
+
+// One new cache position of one kv head, by the lanes t = 0 .. D/2 - 1 of one wave (all of them, and
+// no other lane): lane t holds elements t and t + D/2 of the k row (klo, khi: storage-dtype values)
+// and elements 2t, 2t + 1 of the v row (vnew, raw).  Row absmax by a reduction over the D/2 lanes, the
+// scale rule, packed conversion; where `store`, the codes go out as whole words and the scale as one
+// byte, into row `slot` of the blocks kblk / vblk.  Returns the DEQUANTISED rows in place -- what
+// every later read of the slot sees.
+template <int DT, int D>
+__device__ __forceinline__ void kv8_put_row(float &klo, float &khi, uint32_t &vnew, int t, bool store,
+                                            unsigned char *kblk, unsigned char *vblk, int slot) {
+  constexpr int H2 = D / 2;
+  const float v0 = from_bits<DT>(vnew), v1 = from_bits<DT>(vnew >> 16);
+  uint32_t ka = max(__float_as_uint(klo) & 0x7FFFFFFFu, __float_as_uint(khi) & 0x7FFFFFFFu);
+  uint32_t va = max(__float_as_uint(v0) & 0x7FFFFFFFu, __float_as_uint(v1) & 0x7FFFFFFFu);
+#pragma unroll
+  for (int o = H2 / 2; o > 0; o >>= 1) {
+    ka = max(ka, (uint32_t)__shfl_xor((int)ka, o, kWave));
+    va = max(va, (uint32_t)__shfl_xor((int)va, o, kWave));
+  }
+  const uint32_t ks = kv8_scale_byte<DT>(ka), vs = kv8_scale_byte<DT>(va);
+  const uint32_t kc = kv8_quant2(klo, khi, ks), vc = kv8_quant2(v0, v1, vs);
+  // whole words: lane 4i gathers the k codes of lanes 4i .. 4i + 3, lane 2i the v codes of 2i, 2i + 1
+  const uint32_t k1 = (uint32_t)__shfl_down((int)kc, 1, kWave), k2 = (uint32_t)__shfl_down((int)kc, 2, kWave);
+  const uint32_t k3 = (uint32_t)__shfl_down((int)kc, 3, kWave), vn = (uint32_t)__shfl_down((int)vc, 1, kWave);
+  if (store) {
+    unsigned char *kd = kblk + slot * D, *vd = vblk + slot * D;
+    if ((t & 3) == 0) {
+      reinterpret_cast<uint32_t *>(kd)[t >> 2] = (kc & 0xFFu) | (k1 & 0xFFu) << 8 | (k2 & 0xFFu) << 16 | (k3 & 0xFFu) << 24;
+      reinterpret_cast<uint32_t *>(kd)[(t + H2) >> 2] = (kc >> 8) | (k1 >> 8) << 8 | (k2 >> 8) << 16 | (k3 >> 8) << 24;
+    }
+    if ((t & 1) == 0) reinterpret_cast<uint32_t *>(vd)[t >> 1] = vc | vn << 16;
+    if (t == 0) {
+      kblk[Kv8<D>::kScales + slot] = (unsigned char)ks;
+      vblk[Kv8<D>::kScales + slot] = (unsigned char)vs;
+    }
+  }
+  const uint32_t kq = ks == 255u ? kKv8Nan2<DT> : kv8_dq2<DT, false>(kc, kv8_scale_f32(ks));
+  klo = from_bits<DT>(kq);
+  khi = from_bits<DT>(kq >> 16);
+  vnew = vs == 255u ? kKv8Nan2<DT> : kv8_dq2<DT, false>(vc, kv8_scale_f32(vs));
+}
+
 // LDS of one head's attention.  `v` is the staged v rows, kAttnChunk x H2 words with the word
 // columns XOR-swizzled by (position & 31): a thread writes its half row at one column across 32
 // consecutive positions per instruction, so an unswizzled 64-word row put every lane of a write
@@ -132,12 +221,17 @@ template <int D> struct AttnLds {
 // entry -- uniform over the workgroup -- beside the position and checked it against [0, P)), at
 // ((page Hkv + h) kAttnChunk + (j & 127)) D: the first cache row is chosen so that every address
 // below, the new token's slot included, is the contiguous form's expression.
-template <int DT, int D, bool STREAMS = false, bool VERIFY = false, bool PAGED = false>
+// KV8 (with PAGED): the pools hold kv8 blocks.  A thread loads the codes of its half rows and the rows'
+// scale bytes and converts them to packed 16-bit pairs where the 16-bit form unpacks its loads; the new
+// token's rows are quantised, stored and DEQUANTISED before they go to s_kn / s_vn, so the step
+// scores what every later step reads back.  Everything from kw[] / vw[] on is the same code.
+template <int DT, int D, bool STREAMS = false, bool VERIFY = false, bool PAGED = false, bool KV8 = false>
 __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, int split, int hq, int b,
                                                       const AttnLds<D> &S, int cb = 0, long long pv = 0,
                                                       int page = 0) {
   static_assert(STREAMS || !VERIFY, "the verify form computes its mask from the position");
   static_assert(STREAMS || !PAGED, "the paged form has a position per stream");
+  static_assert(PAGED || !KV8, "kv8 rows live in page pools");
   constexpr int ES = DT == QZ_DT_F32 ? 4 : 2;
   static_assert(ES == 2, "16-bit activations and caches");
   constexpr int H2 = D / 2;      // rotary half; also the share of a row one thread dots
@@ -185,18 +279,26 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
   unsigned char mk;
   if constexpr (STREAMS) mk = (in_l && j <= p) ? (unsigned char)1 : (unsigned char)0;
   else mk = in_l ? a.mask[(long long)b * a.mb + j * a.mj] : (unsigned char)0;
-  u32x4 kr[NW / 4], vr[NW / 4];
+  constexpr int NR = KV8 ? NW / 8 : NW / 4;   // 16-B loads of half a row
+  u32x4 kr[NR], vr[NR];
+  uint32_t ksb = 127u, vsb = 127u;            // KV8: the rows' scale bytes
   const bool spec = L <= kAttnSpecL;
-  const u32x4 *kp = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(a.kc) + ((crow + j) * D + half * H2) * ES);
-  const u32x4 *vp = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(a.vc) + ((crow + j) * D + half * H2) * ES);
+  const long long blk8 = KV8 ? ((long long)page * a.Hkv + h) * Kv8<D>::kBlock : 0;   // KV8: this (page, kv head)
+  const long long roff = KV8 ? blk8 + pos_i * D + half * H2 : ((crow + j) * D + half * H2) * ES;
+  const u32x4 *kp = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(a.kc) + roff);
+  const u32x4 *vp = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(a.vc) + roff);
   if (in_l && spec && (kAttnAbl & 2) == 0) {
 #pragma unroll
-    for (int i = 0; i < NW / 4; ++i) kr[i] = kp[i];
+    for (int i = 0; i < NR; ++i) kr[i] = kp[i];
 #pragma unroll
-    for (int i = 0; i < NW / 4; ++i) vr[i] = vp[i];
+    for (int i = 0; i < NR; ++i) vr[i] = vp[i];
+    if constexpr (KV8) {
+      ksb = reinterpret_cast<const unsigned char *>(a.kc)[blk8 + Kv8<D>::kScales + pos_i];
+      vsb = reinterpret_cast<const unsigned char *>(a.vc)[blk8 + Kv8<D>::kScales + pos_i];
+    }
   } else {
 #pragma unroll
-    for (int i = 0; i < NW / 4; ++i) kr[i] = vr[i] = u32x4{0u, 0u, 0u, 0u};
+    for (int i = 0; i < NR; ++i) kr[i] = vr[i] = u32x4{0u, 0u, 0u, 0u};
   }
   __builtin_amdgcn_sched_barrier(0);
 
@@ -216,7 +318,10 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
     reinterpret_cast<uint16_t *>(s_qh)[t + H2] = (uint16_t)bits_dt<DT>(hi);
     if (mine) {
       rope(k1, k2, lo, hi);
-      if (gq == 0) {
+      if constexpr (KV8) {
+        kv8_put_row<DT, D>(lo, hi, vnew, t, gq == 0, reinterpret_cast<unsigned char *>(a.kc) + blk8,
+                           reinterpret_cast<unsigned char *>(a.vc) + blk8, (int)(p & (kAttnChunk - 1)));
+      } else if (gq == 0) {
         char *kd = reinterpret_cast<char *>(a.kc) + (crow + p) * D * ES;
         char *vd = reinterpret_cast<char *>(a.vc) + (crow + p) * D * ES;
         store_f32<DT>(kd, t, lo);
@@ -244,14 +349,28 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
     const bool ok = mk != 0;
     if (!spec && ok && (VERIFY || j != p)) {  // long cache: the rows the mask keeps, read now
 #pragma unroll
-      for (int i = 0; i < NW / 4; ++i) kr[i] = kp[i];
+      for (int i = 0; i < NR; ++i) kr[i] = kp[i];
 #pragma unroll
-      for (int i = 0; i < NW / 4; ++i) vr[i] = vp[i];
+      for (int i = 0; i < NR; ++i) vr[i] = vp[i];
+      if constexpr (KV8) {
+        ksb = reinterpret_cast<const unsigned char *>(a.kc)[blk8 + Kv8<D>::kScales + pos_i];
+        vsb = reinterpret_cast<const unsigned char *>(a.vc)[blk8 + Kv8<D>::kScales + pos_i];
+      }
     }
     uint32_t kw[NW], vw[NW];
     if (!VERIFY && ok && j == p) {
 #pragma unroll
       for (int i = 0; i < NW; ++i) { kw[i] = s_kn[half * NW + i]; vw[i] = s_vn[half * NW + i]; }
+    } else if constexpr (KV8) {
+#pragma unroll
+      for (int i = 0; i < NR; ++i) {
+        kv8_dq16<DT>(kr[i], ksb, &kw[8 * i]);
+        kv8_dq16<DT>(vr[i], vsb, &vw[8 * i]);
+      }
+      if (!ok) {
+#pragma unroll
+        for (int i = 0; i < NW; ++i) kw[i] = vw[i] = 0u;
+      }
     } else {
 #pragma unroll
       for (int i = 0; i < NW / 4; ++i) {

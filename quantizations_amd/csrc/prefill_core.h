@@ -63,7 +63,11 @@ template <int DT> __device__ __forceinline__ pf_f4 pf_mfma(const u32x4 a, const 
 // [0, P) is never turned into an address: its keys are staged as zeros and every row that can see
 // one of them (position >= 128 (jt >> 1)) is NaN.  A row below it masks those keys to weight 0 as it
 // does the real keys it cannot see, and keeps the contiguous kernel's bits.
-template <int DT, int D, bool PAGED>
+// KV8 (with PAGED, paged_attn_kv8.hip): the pools hold kv8 blocks (attn_core.h).  load_tile reads 16
+// codes per 16-B load and the key's scale byte -- half the loads and half the registers in flight
+// during the MFMAs; store_tile converts them in registers and writes the same LDS image, so the
+// MFMA loop sees the 16-bit operands of the paged kernel on the dequantised cache.
+template <int DT, int D, bool PAGED, bool KV8 = false>
 __device__ __forceinline__ void prefill_attn_tile(const PrefillArgs &a) {
   constexpr int ES = 2;
   constexpr int NCH = D / 8;            // 16-B chunks of a row
@@ -138,11 +142,35 @@ __device__ __forceinline__ void prefill_attn_tile(const PrefillArgs &a) {
   // key tile jt: global -> registers (rows above pmax: zeros, never the cache's contents)
   const u32x4 *kg = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(a.kc) + ((long long)b * a.Hkv + h) * L * D * ES);
   const u32x4 *vg = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(a.vc) + ((long long)b * a.Hkv + h) * L * D * ES);
-  u32x4 kr[NLD], vr[NLD];
+  static_assert(PAGED || !KV8, "kv8 rows live in page pools");
+  constexpr int NLR = KV8 ? NLD / 2 : NLD;   // 16-B loads in flight per thread and operand
+  u32x4 kr[NLR], vr[NLR];
+  uint32_t ksc[NLR], vsc[NLR];               // KV8: the scale bytes of the loads' keys
   const int *const trow = PAGED ? a.table + (long long)b * a.trow : nullptr;
   int bad_key = 0x7FFFFFFF;   // PAGED: the first position behind an invalid entry
   auto load_tile = [&](int jt, int pg) {
-    if constexpr (PAGED) {
+    if constexpr (KV8) {
+      const bool okp = (unsigned)pg < (unsigned)a.P;
+      if (!okp) bad_key = min(bad_key, (jt >> 1) * kAttnChunk);
+      const long long blk = okp ? ((long long)pg * a.Hkv + h) * Kv8<D>::kBlock : 0;
+      const unsigned char *kb = reinterpret_cast<const unsigned char *>(a.kc) + blk;
+      const unsigned char *vb = reinterpret_cast<const unsigned char *>(a.vc) + blk;
+#pragma unroll
+      for (int n = 0; n < NLR; ++n) {
+        const int ci = n * 256 + t, key = ci / (NCH / 2), c8 = ci - key * (NCH / 2);
+        const int j = jt * kPfTK + key, row = (jt & 1) * kPfTK + key;
+        u32x4 kn = u32x4{0u, 0u, 0u, 0u}, vn = kn;
+        uint32_t ksn = 127u, vsn = 127u;
+        if (okp && j <= pmax) {
+          kn = *reinterpret_cast<const u32x4 *>(kb + row * D + (c8 << 4));
+          vn = *reinterpret_cast<const u32x4 *>(vb + row * D + (c8 << 4));
+          ksn = kb[Kv8<D>::kScales + row];
+          vsn = vb[Kv8<D>::kScales + row];
+        }
+        kr[n] = kn; vr[n] = vn;
+        ksc[n] = ksn; vsc[n] = vsn;
+      }
+    } else if constexpr (PAGED) {
       const bool okp = (unsigned)pg < (unsigned)a.P;
       if (!okp) bad_key = min(bad_key, (jt >> 1) * kAttnChunk);
       // row of the tile's key 0 less jt * kPfTK: the index expression below stays the contiguous one
@@ -177,11 +205,28 @@ __device__ __forceinline__ void prefill_attn_tile(const PrefillArgs &a) {
     }
   };
   auto store_tile = [&]() {
+    if constexpr (KV8) {
 #pragma unroll
-    for (int n = 0; n < NLD; ++n) {
-      const int ci = n * 256 + t, key = ci / NCH, ch = ci - key * NCH;
-      *reinterpret_cast<u32x4 *>(s_k + key * KROW + ((ch ^ (key & (NCH - 1))) << 4)) = kr[n];
-      *reinterpret_cast<u32x4 *>(s_v + key * VROW + (ch << 4)) = vr[n];
+      for (int n = 0; n < NLR; ++n) {
+        const int ci = n * 256 + t, key = ci / (NCH / 2), c8 = ci - key * (NCH / 2);
+        uint32_t kw[8], vw[8];
+        kv8_dq16<DT>(kr[n], ksc[n], kw);
+        kv8_dq16<DT>(vr[n], vsc[n], vw);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int ch = 2 * c8 + u;
+          *reinterpret_cast<u32x4 *>(s_k + key * KROW + ((ch ^ (key & (NCH - 1))) << 4)) =
+              u32x4{kw[4 * u], kw[4 * u + 1], kw[4 * u + 2], kw[4 * u + 3]};
+          *reinterpret_cast<u32x4 *>(s_v + key * VROW + (ch << 4)) = u32x4{vw[4 * u], vw[4 * u + 1], vw[4 * u + 2], vw[4 * u + 3]};
+        }
+      }
+    } else {
+#pragma unroll
+      for (int n = 0; n < NLD; ++n) {
+        const int ci = n * 256 + t, key = ci / NCH, ch = ci - key * NCH;
+        *reinterpret_cast<u32x4 *>(s_k + key * KROW + ((ch ^ (key & (NCH - 1))) << 4)) = kr[n];
+        *reinterpret_cast<u32x4 *>(s_v + key * VROW + (ch << 4)) = vr[n];
+      }
     }
   };
   load_tile(0, PAGED ? trow[0] : 0);

@@ -366,8 +366,19 @@ def _single_gpu_prepared(model, who: str) -> torch.device:
     return dev
 
 
+def _check_kv_dtype(kv_dtype, who: str, kv_pages=0) -> None:
+    if kv_dtype is None:
+        return
+    if kv_dtype != "fp8":
+        raise ValueError(f"{who}: kv_dtype must be None (the model's 16-bit dtype) or 'fp8', not {kv_dtype!r}")
+    if kv_pages is None:
+        raise ValueError(f"{who}: kv_dtype='fp8' is a format of the paged cache's pages; open the session with "
+                         "kv_pages (the contiguous StaticCache stays 16-bit)")
+
+
 class PagedLayer:
-    """One layer of a PagedKVCache: the K and V page pools [P, Hkv, 128, D] as keys / values."""
+    """One layer of a PagedKVCache: the K and V page pools [P, Hkv, 128, D] (kv_dtype="fp8": uint8
+    [P, Hkv, 128 (D + 1)]) as keys / values."""
 
     def __init__(self, keys: torch.Tensor, values: torch.Tensor):
         self.keys, self.values = keys, values
@@ -377,15 +388,27 @@ class PagedKVCache:
     """What a paged session hands the decoder as past_key_values: per layer one K and one V pool of
     num_pages pages (zero-filled: a page nobody wrote yet holds finite data).  With position_ids and
     a 4-D mask given, the decoder's forward asks nothing of it, and the fused attention reads
-    .layers[i] only; anything that tried to use it as a transformers cache ends in update()."""
+    .layers[i] only; anything that tried to use it as a transformers cache ends in update().
+    kv_dtype="fp8": the pools are kv8 byte pools, uint8 [P, Hkv, 128 (D + 1)] -- per (page, kv head) 128 D
+    E4M3 codes, then 128 power-of-two scale bytes (csrc/paged_attn_kv8.hip) -- which the *_paged_kv8
+    launches read and write; a zero-filled page reads as zeros there too.  A page is still pool[page]."""
 
-    def __init__(self, config, num_pages: int, dtype, device):
+    def __init__(self, config, num_pages: int, dtype, device, kv_dtype: Optional[str] = None):
+        _check_kv_dtype(kv_dtype, "PagedKVCache")
         head_dim = getattr(config, "head_dim", None) or config.hidden_size // config.num_attention_heads
-        shape = (int(num_pages), config.num_key_value_heads, _ops.KV_PAGE, head_dim)
+        self.kv_dtype = kv_dtype
+        if kv_dtype == "fp8":
+            if head_dim not in (64, 128):
+                raise ValueError(f"PagedKVCache: kv_dtype='fp8' takes head_dim 64 or 128, not {head_dim}")
+            shape = (int(num_pages), config.num_key_value_heads, _ops.KV_PAGE * (head_dim + _ops.KV8_ROW_EXTRA))
+            dtype = torch.uint8
+        else:
+            shape = (int(num_pages), config.num_key_value_heads, _ops.KV_PAGE, head_dim)
         self.layers = [PagedLayer(torch.zeros(shape, dtype=dtype, device=device),
                                   torch.zeros(shape, dtype=dtype, device=device))
                        for _ in range(config.num_hidden_layers)]
-        self.bytes_per_page = 2 * len(self.layers) * shape[1] * shape[2] * shape[3] * self.layers[0].keys.element_size()
+        keys = self.layers[0].keys
+        self.bytes_per_page = 2 * len(self.layers) * (keys.numel() // shape[0]) * keys.element_size()
 
     def update(self, *args, **kwargs):
         raise RuntimeError("PagedKVCache: keys and values are written by the paged attention launches "
@@ -428,10 +451,15 @@ class StreamSession:
     full pages and lets admit() map the resident pages of an equal prefix into the new row, running
     the windows behind them only.  None of this recaptures: the table is a device buffer.
     A shared page carries the bits its donor computed; a newcomer's tokens equal those of its own
-    full prefill bit for bit when the donor ran the same windows."""
+    full prefill bit for bit when the donor ran the same windows.
+
+    kv_dtype (None: the model's 16-bit dtype; "fp8" needs kv_pages): the pages hold kv8 rows, D E4M3
+    codes and one power-of-two scale byte per row, in (D + 1) / 2D of the bytes; everything above works
+    unchanged, and a step scores the new token as every later step reads it back."""
 
     def __init__(self, model, batch: int, max_len: int, *, graph: bool = True, prefill_chunk: Optional[int] = None,
-                 kv_pages: Optional[int] = None, prefix_cache: bool = False):
+                 kv_pages: Optional[int] = None, prefix_cache: bool = False, kv_dtype: Optional[str] = None):
+        _check_kv_dtype(kv_dtype, "StreamSession", kv_pages)
         if batch < 1 or max_len < 2:
             raise ValueError("StreamSession: batch must be positive and max_len at least 2")
         if prefill_chunk is not None and int(prefill_chunk) < 1:
@@ -453,7 +481,8 @@ class StreamSession:
             from .kv_pages import KVPagePool
 
             self.pages = KVPagePool(int(kv_pages), self.batch, -(-self.max_len // _ops.KV_PAGE), dev)
-            self.cache = PagedKVCache(model.config, int(kv_pages), model.get_input_embeddings().weight.dtype, dev)
+            self.cache = PagedKVCache(model.config, int(kv_pages), model.get_input_embeddings().weight.dtype, dev,
+                                      kv_dtype=kv_dtype)
             self._extra = {"_qz_paged": (self.pages.table,)}
         else:
             self.cache = StaticCache(config=model.config, max_cache_len=self.max_len)
@@ -862,7 +891,7 @@ class SpeculativeSession(StreamSession):
 
     def __init__(self, model, batch: int, max_len: int, *, draft_tokens: int = 3, ngram: int = 3, graph: bool = True,
                  sample: bool = False, prefill_chunk: Optional[int] = None, kv_pages: Optional[int] = None,
-                 prefix_cache: bool = False):
+                 prefix_cache: bool = False, kv_dtype: Optional[str] = None):
         from .core import MT_MAX_TOKENS
 
         if int(draft_tokens) < 1:
@@ -874,7 +903,7 @@ class SpeculativeSession(StreamSession):
             raise ValueError(f"SpeculativeSession: batch * (draft_tokens + 1) = {batch * T} rows per step, the "
                              f"multi-token kernels take {MT_MAX_TOKENS}")
         super().__init__(model, batch, max_len, graph=graph, prefill_chunk=prefill_chunk, kv_pages=kv_pages,
-                         prefix_cache=prefix_cache)
+                         prefix_cache=prefix_cache, kv_dtype=kv_dtype)
         dev = self.device
         self.T, self.ngram, self.sample = T, int(ngram), bool(sample)
         self.tok = torch.zeros((batch, T), dtype=torch.int64, device=dev)
@@ -939,13 +968,15 @@ class SpeculativeSession(StreamSession):
 
 def _speculative_session(model, batch: int, max_len: int, prompt_lookup_num_tokens, max_matching_ngram_size,
                          do_sample: bool, graph: bool, who: str, sampling: bool = False,
-                         prefill_chunk: Optional[int] = None, kv_pages: Optional[int] = None) -> SpeculativeSession:
+                         prefill_chunk: Optional[int] = None, kv_pages: Optional[int] = None,
+                         kv_dtype: Optional[str] = None) -> SpeculativeSession:
     if do_sample and not sampling:
         raise ValueError(f"{who}: prompt_lookup_num_tokens verifies drafts against the greedy token; "
                          "do_sample is not supported with it unless prompt_lookup_sampling=True")
     n = PROMPT_LOOKUP_NGRAM if max_matching_ngram_size is None else int(max_matching_ngram_size)
     return SpeculativeSession(model, batch, max_len, draft_tokens=int(prompt_lookup_num_tokens), ngram=n, graph=graph,
-                              sample=bool(do_sample and sampling), prefill_chunk=prefill_chunk, kv_pages=kv_pages)
+                              sample=bool(do_sample and sampling), prefill_chunk=prefill_chunk, kv_pages=kv_pages,
+                              kv_dtype=kv_dtype)
 
 
 def _run_speculative(sess: SpeculativeSession, max_new_tokens: int) -> None:
@@ -996,7 +1027,7 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
                     max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False,
                     repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
                     no_repeat_ngram_size=None, min_new_tokens=None, prefill_chunk: Optional[int] = None,
-                    kv_pages: Optional[int] = None) -> list:
+                    kv_pages: Optional[int] = None, kv_dtype: Optional[str] = None) -> list:
     """generate() for prompts of different lengths: `prompts` are 1-D int64 tensors; returns one 1-D
     int64 tensor per prompt on the model's device, the prompt followed by up to max_new_tokens picked
     tokens of its own, ending with eos_token_id if the stream picked it.  A stream that stopped writes
@@ -1011,7 +1042,8 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     prefill_chunk: the session's (StreamSession): None keeps the whole-prompt forward, an int runs the
     prompts through layer_ops.prefill_attention in windows of that many tokens.
     kv_pages: the session's: that many pages of 128 positions per layer in place of a cache row of
-    Smax + max_new_tokens positions per prompt (needs prefill_chunk)."""
+    Smax + max_new_tokens positions per prompt (needs prefill_chunk).
+    kv_dtype: the session's: "fp8" keeps the pages as kv8 rows (needs kv_pages)."""
     prompts = list(prompts)
     if not prompts or any((not isinstance(p, torch.Tensor)) or p.dim() != 1 or p.numel() < 1 for p in prompts):
         raise ValueError("generate_ragged: prompts must be a non-empty sequence of non-empty 1-D tensors")
@@ -1022,12 +1054,12 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     if prompt_lookup_num_tokens is not None:
         sess = _speculative_session(model, B, Smax + max_new_tokens, prompt_lookup_num_tokens,
                                     max_matching_ngram_size, do_sample, graph, "generate_ragged",
-                                    prompt_lookup_sampling, prefill_chunk, kv_pages)
+                                    prompt_lookup_sampling, prefill_chunk, kv_pages, kv_dtype)
     elif max_matching_ngram_size is not None:
         raise ValueError("generate_ragged: max_matching_ngram_size needs prompt_lookup_num_tokens")
     else:
         sess = StreamSession(model, B, Smax + max_new_tokens, graph=graph, prefill_chunk=prefill_chunk,
-                             kv_pages=kv_pages)
+                             kv_pages=kv_pages, kv_dtype=kv_dtype)
     if do_sample:
         sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
         sess.seed(generator)

@@ -310,7 +310,8 @@ def _fused_attention_forward(mod: nn.Module, orig):
     PagedKVCache) and table is the int32 [B, NP] page table all layers share.  The layer runs the
     paged twin of that keyword's launch (layer_ops.decode_attention_paged, decode_attention_verify_paged,
     prefill_attention_paged; a prefill window's streams are rows row0 .. row0 + nb - 1 of the table)
-    -- or raises."""
+    -- or raises.  Where the layer's pools are uint8 (PagedKVCache(kv_dtype="fp8"): kv8 blocks
+    [P, Hkv, 128 (D + 1)]) the layer runs the *_paged_kv8 launch of the same keyword instead."""
     from . import layer_ops
     from .layer_ops import (decode_attention, decode_attention_streams, decode_attention_streams_supported,
                             decode_attention_supported, decode_attention_verify, decode_attention_verify_supported)
@@ -321,12 +322,22 @@ def _fused_attention_forward(mod: nn.Module, orig):
             raise ValueError("_qz_paged goes with exactly one of _qz_stream_pos, _qz_verify_pos and _qz_prefill")
         layers, idx = getattr(past_key_values, "layers", None), getattr(mod, "layer_idx", None)
         layer = layers[idx] if layers is not None and idx is not None and idx < len(layers) else None
+        kv8 = layer is not None and type(layer).__name__ == "PagedLayer" and layer.keys.dtype == torch.uint8
         if (layer is None or type(layer).__name__ != "PagedLayer" or hidden_states.dim() != 3
                 or position_embeddings is None or kwargs.get("output_attentions", False) or mod.training
-                or layer.keys.dim() != 4 or layer.keys.shape[-1] != mod.head_dim):
+                or (layer.keys.dim() != 4 or layer.keys.shape[-1] != mod.head_dim) and not kv8
+                or kv8 and (layer.keys.dim() != 3 or layer.keys.shape[-1] != layer_ops.KV_PAGE
+                            * (mod.head_dim + layer_ops.KV8_ROW_EXTRA))):
             raise ValueError("_qz_paged: the paged launches need a PagedKVCache layer of this module's head_dim")
         table, = paged
         keys, values = layer.keys, layer.values
+        sfx = "_kv8" if kv8 else ""
+        prefill_paged, prefill_ok = (getattr(layer_ops, "prefill_attention_paged" + sfx),
+                                     getattr(layer_ops, "prefill_attention_paged" + sfx + "_supported"))
+        verify_paged, verify_ok = (getattr(layer_ops, "decode_attention_verify_paged" + sfx),
+                                   getattr(layer_ops, "decode_attention_verify_paged" + sfx + "_supported"))
+        decode_paged, decode_ok = (getattr(layer_ops, "decode_attention_paged" + sfx),
+                                   getattr(layer_ops, "decode_attention_paged" + sfx + "_supported"))
         cos, sin = position_embeddings
         nq = keys.shape[1] * (mod.config.num_attention_heads // mod.config.num_key_value_heads)
         if prefill is not None:
@@ -335,11 +346,11 @@ def _fused_attention_forward(mod: nn.Module, orig):
             if not (isinstance(row0, int) and 0 <= row0 and row0 + nb <= table.shape[0]):
                 raise ValueError("_qz_paged: rows row0 .. row0 + nb - 1 are not rows of the table")
             table = table[row0:row0 + nb]
-            ok = layer_ops.prefill_attention_paged_supported(hidden_states, cos, keys, values, table, pos, length, nq)
+            ok = prefill_ok(hidden_states, cos, keys, values, table, pos, length, nq)
         elif verify_pos is not None:
-            ok = layer_ops.decode_attention_verify_paged_supported(hidden_states, cos, keys, values, table, verify_pos, nq)
+            ok = verify_ok(hidden_states, cos, keys, values, table, verify_pos, nq)
         else:
-            ok = layer_ops.decode_attention_paged_supported(hidden_states, cos, keys, values, table, stream_pos, nq)
+            ok = decode_ok(hidden_states, cos, keys, values, table, stream_pos, nq)
         if not ok:
             raise ValueError("_qz_paged: the paged launch does not take these shapes/dtypes/layout")
         q = mod.q_proj(hidden_states)
@@ -348,12 +359,11 @@ def _fused_attention_forward(mod: nn.Module, orig):
         if q.shape[-1] != nq * mod.head_dim or k.shape[-1] != keys.shape[1] * mod.head_dim:
             raise ValueError("_qz_paged: the projections' widths differ from the pools' heads")
         if prefill is not None:
-            out = layer_ops.prefill_attention_paged(q, k, v, cos, sin, keys, values, table, pos, length, nq, mod.scaling)
+            out = prefill_paged(q, k, v, cos, sin, keys, values, table, pos, length, nq, mod.scaling)
         elif verify_pos is not None:
-            out = layer_ops.decode_attention_verify_paged(q, k, v, cos, sin, keys, values, table, verify_pos, nq,
-                                                          mod.scaling)
+            out = verify_paged(q, k, v, cos, sin, keys, values, table, verify_pos, nq, mod.scaling)
         else:
-            out = layer_ops.decode_attention_paged(q, k, v, cos, sin, keys, values, table, stream_pos, nq, mod.scaling)
+            out = decode_paged(q, k, v, cos, sin, keys, values, table, stream_pos, nq, mod.scaling)
         return _project(mod.o_proj, out, residual), None
 
     def prefill_forward(hidden_states, position_embeddings, past_key_values, spec, residual, kwargs):

@@ -418,22 +418,44 @@ def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: to
 KV_PAGE = 128  # positions per page of the paged cache (qz_kv_page_size(): the decode head's key chunk)
 
 
-def _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads: int, min_t: int, cos_batches) -> bool:
-    """What the three paged launches ask of the activations, the pools [P, Hkv, 128, D], the table
-    int32 [B, NP] with unit inner stride, pos int64 [B] and cos/sin [*, T, D]."""
+KV8_ROW_EXTRA = 1  # bytes a kv8 cache row carries beyond its D codes: the scale byte
+
+
+def _kv8_geometry(k_pool, v_pool):
+    """(P, Hkv, D) of a pair of kv8 pools, uint8 [P, Hkv, 128 (D + 1)]; None for anything else."""
+    if not (isinstance(k_pool, torch.Tensor) and isinstance(v_pool, torch.Tensor) and k_pool.dim() == 3
+            and v_pool.shape == k_pool.shape and k_pool.dtype == torch.uint8):
+        return None
+    P, Hkv, W = k_pool.shape
+    D = W // KV_PAGE - KV8_ROW_EXTRA
+    return (P, Hkv, D) if W == KV_PAGE * (D + KV8_ROW_EXTRA) else None
+
+
+def _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads: int, min_t: int, cos_batches,
+                              kv8: bool = False) -> bool:
+    """What the three paged launches ask of the activations, the pools [P, Hkv, 128, D] (kv8: uint8
+    [P, Hkv, 128 (D + 1)]), the table int32 [B, NP] with unit inner stride, pos int64 [B] and cos/sin
+    [*, T, D]."""
     if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype in (torch.float16, torch.bfloat16)
             and q.dim() == 3 and q.shape[1] >= min_t) or _needs_grad(q):
         return False
-    if not (isinstance(k_pool, torch.Tensor) and isinstance(v_pool, torch.Tensor) and k_pool.dim() == 4
-            and v_pool.shape == k_pool.shape and k_pool.shape[2] == KV_PAGE):
-        return False
-    P, Hkv, _, D = k_pool.shape
+    if kv8:
+        geometry = _kv8_geometry(k_pool, v_pool)
+        if geometry is None:
+            return False
+        P, Hkv, D = geometry
+    else:
+        if not (isinstance(k_pool, torch.Tensor) and isinstance(v_pool, torch.Tensor) and k_pool.dim() == 4
+                and v_pool.shape == k_pool.shape and k_pool.shape[2] == KV_PAGE):
+            return False
+        P, Hkv, _, D = k_pool.shape
     B, T = q.shape[0], q.shape[1]
     if (D not in (64, 128) or Hkv == 0 or P == 0 or num_heads % Hkv or num_heads // Hkv > 8 or B > 65535
             or num_heads > 65535):
         return False
     for t in (k_pool, v_pool):
-        if t.dtype != q.dtype or t.device != q.device or not t.is_contiguous() or t.data_ptr() % 16:
+        if (t.dtype != (torch.uint8 if kv8 else q.dtype) or t.device != q.device or not t.is_contiguous()
+                or t.data_ptr() % 16):
             return False
     if not (isinstance(table, torch.Tensor) and table.dtype == torch.int32 and table.dim() == 2
             and table.shape[0] == B and table.shape[1] >= 1 and table.device == q.device
@@ -577,6 +599,135 @@ def prefill_attention_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, c
         vs, c2.data_ptr(), s2.data_ptr(), cs, k_pool.data_ptr(), v_pool.data_ptr(), table.data_ptr(), table.stride(0),
         pos.data_ptr(), length.data_ptr(), out.data_ptr(), num_heads * D, float(scale), _lib.stream_of(q)),
         "qz_prefill_attention_paged")
+    return out
+
+
+def decode_attention_paged_kv8_supported(q: torch.Tensor, cos: torch.Tensor, k_pool: torch.Tensor,
+                                         v_pool: torch.Tensor, table, pos, num_heads: int) -> bool:
+    """What qz_decode_attention_paged_kv8 takes: decode_attention_paged_supported's operands with kv8
+    pools, uint8 [P, Hkv, 128 (D + 1)] with D in {64, 128}, contiguous and 16-B aligned, in place of the
+    16-bit ones.  Metadata only."""
+    return (isinstance(q, torch.Tensor) and q.dim() == 3 and q.shape[1] == 1
+            and _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 1, lambda B: (1, B), True))
+
+
+def decode_attention_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor,
+                               sin: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, table: torch.Tensor,
+                               pos: torch.Tensor, num_heads: int, scale: float) -> torch.Tensor:
+    """decode_attention_paged over kv8 pools (qz_decode_attention_paged_kv8): a cache row is D E4M3
+    codes and a power-of-two scale byte.  The new token's rotated k and its v are quantised, stored,
+    and scored as they will read back, so the output carries the bits of decode_attention_paged with
+    identity cos/sin on the dequantised pools, the rotated q and the dequantised new rows.  Validity
+    rules are decode_attention_paged's.  Returns [B, 1, Hq*D]."""
+    if not decode_attention_paged_kv8_supported(q, cos, k_pool, v_pool, table, pos, num_heads):
+        raise ValueError("decode_attention_paged_kv8: unsupported shapes/dtypes/layout")
+    P, Hkv, D = _kv8_geometry(k_pool, v_pool)
+    B, NP = table.shape
+    # _attention_launch_operands reads only the shape of its cache operand: [B, Hkv, L, D]
+    shape = q.as_strided((B, Hkv, NP * KV_PAGE, D), (0, 0, 0, 0))
+    q2, k2, v2, out, work, cs_row = _attention_launch_operands("decode_attention_paged_kv8", q, k, v, cos, sin, shape,
+                                                               num_heads)
+    _lib.check(_lib.lib.qz_decode_attention_paged_kv8(
+        _lib.dtype_code(q.dtype), B, num_heads, Hkv, D, NP, P, q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0),
+        v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cs_row, k_pool.data_ptr(), v_pool.data_ptr(),
+        table.data_ptr(), table.stride(0), pos.data_ptr(), out.data_ptr(), num_heads * D,
+        work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)),
+        "qz_decode_attention_paged_kv8")
+    return out
+
+
+def decode_attention_verify_paged_kv8_supported(q: torch.Tensor, cos: torch.Tensor, k_pool: torch.Tensor,
+                                                v_pool: torch.Tensor, table, pos, num_heads: int) -> bool:
+    """What qz_decode_attention_verify_paged_kv8 takes: decode_attention_verify_paged_supported's
+    operands with kv8 pools.  Metadata only."""
+    if not _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 2, lambda B: (B,), True):
+        return False
+    B, T = q.shape[0], q.shape[1]
+    return B * T <= 65535 and (B == 1 or cos.stride(0) == T * cos.stride(1))
+
+
+def decode_attention_verify_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor,
+                                      sin: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                                      table: torch.Tensor, pos: torch.Tensor, num_heads: int,
+                                      scale: float) -> torch.Tensor:
+    """decode_attention_verify_paged over kv8 pools (qz_decode_attention_verify_paged_kv8): the T new
+    rows of every stream are rotated, quantised and stored first, then every token reads its keys,
+    slot pos[b] + i included, from the pools.  One call equals T successive decode_attention_paged_kv8
+    calls in outputs and pool bytes.  Returns [B, T, Hq*D]."""
+    if not decode_attention_verify_paged_kv8_supported(q, cos, k_pool, v_pool, table, pos, num_heads):
+        raise ValueError("decode_attention_verify_paged_kv8: unsupported shapes/dtypes/layout")
+    P, Hkv, D = _kv8_geometry(k_pool, v_pool)
+    B, NP = table.shape
+    T, G = q.shape[1], num_heads // Hkv
+    if q.shape[2] != num_heads * D:
+        raise ValueError("decode_attention_verify_paged_kv8: q width differs from num_heads * head_dim")
+    if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
+        raise ValueError("decode_attention_verify_paged_kv8: sin must match cos")
+    if k.shape[:2] != q.shape[:2] or v.shape[:2] != q.shape[:2]:
+        raise ValueError("decode_attention_verify_paged_kv8: k/v must hold q's [B, T] rows")
+    R = B * T
+    q2, k2, v2 = (t.reshape(R, -1) for t in (q, k, v))
+    k2 = k2 if k2.stride(-1) == 1 else k2.contiguous()
+    q2 = q2 if q2.stride(-1) == 1 else q2.contiguous()
+    if v2.stride(-1) != 1 or v2.stride(0) % 2 or v2.data_ptr() % 4:
+        v2 = v2.contiguous()
+    if k2.shape[1] != Hkv * D or v2.shape[1] != Hkv * D:
+        raise ValueError("decode_attention_verify_paged_kv8: k/v width differs from the pools' heads")
+    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
+    work = torch.empty(R * Hkv * NP * G * (D + 2), dtype=torch.float32, device=q.device) if NP > 1 else None
+    _lib.check(_lib.lib.qz_decode_attention_verify_paged_kv8(
+        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, NP, P, q2.data_ptr(), q2.stride(0), k2.data_ptr(),
+        k2.stride(0), v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cos.stride(1), k_pool.data_ptr(),
+        v_pool.data_ptr(), table.data_ptr(), table.stride(0), pos.data_ptr(), out.data_ptr(), num_heads * D,
+        work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)),
+        "qz_decode_attention_verify_paged_kv8")
+    return out
+
+
+def prefill_attention_paged_kv8_supported(q: torch.Tensor, cos: torch.Tensor, k_pool: torch.Tensor,
+                                          v_pool: torch.Tensor, table, pos, length, num_heads: int) -> bool:
+    """What qz_prefill_attention_paged_kv8 takes: prefill_attention_paged_supported's operands with kv8
+    pools.  Metadata only."""
+    if not _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 1, lambda B: (1, B), True):
+        return False
+    return (isinstance(length, torch.Tensor) and length.dtype == torch.int64 and length.dim() == 1
+            and length.shape[0] == q.shape[0] and length.device == q.device and length.is_contiguous())
+
+
+def prefill_attention_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor,
+                                sin: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, table: torch.Tensor,
+                                pos: torch.Tensor, length: torch.Tensor, num_heads: int, scale: float) -> torch.Tensor:
+    """prefill_attention_paged over kv8 pools (qz_prefill_attention_paged_kv8): the window's rows are
+    rotated, quantised and stored, then the tile kernel converts the codes it loads to the 16-bit
+    operands of its MFMAs.  A window split into several calls equals the whole window.  Returns
+    [B, T, Hq*D]."""
+    if not prefill_attention_paged_kv8_supported(q, cos, k_pool, v_pool, table, pos, length, num_heads):
+        raise ValueError("prefill_attention_paged_kv8: unsupported shapes/dtypes/layout")
+    P, Hkv, D = _kv8_geometry(k_pool, v_pool)
+    B, NP = table.shape
+    T = q.shape[1]
+    if q.shape[2] != num_heads * D:
+        raise ValueError("prefill_attention_paged_kv8: q width differs from num_heads * head_dim")
+    if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
+        raise ValueError("prefill_attention_paged_kv8: sin must match cos")
+    if k.shape[:2] != q.shape[:2] or v.shape[:2] != q.shape[:2]:
+        raise ValueError("prefill_attention_paged_kv8: k/v must hold q's [B, T] rows")
+    if k.shape[2] != Hkv * D or v.shape[2] != Hkv * D:
+        raise ValueError("prefill_attention_paged_kv8: k/v width differs from the pools' heads")
+    q2, qs = _token_rows(q, B, T, 16, 8)
+    k2, ks = _token_rows(k, B, T, 2, 1)
+    v2, vs = _token_rows(v, B, T, 4, 2)
+    c2, cs = _token_rows(cos, B, T, 16, 8)
+    s2, ss = _token_rows(sin, B, T, 16, 8)
+    if ss != cs:
+        s2, c2 = s2.contiguous(), c2.contiguous()
+        cs = D
+    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
+    _lib.check(_lib.lib.qz_prefill_attention_paged_kv8(
+        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, NP, P, q2.data_ptr(), qs, k2.data_ptr(), ks, v2.data_ptr(),
+        vs, c2.data_ptr(), s2.data_ptr(), cs, k_pool.data_ptr(), v_pool.data_ptr(), table.data_ptr(), table.stride(0),
+        pos.data_ptr(), length.data_ptr(), out.data_ptr(), num_heads * D, float(scale), _lib.stream_of(q)),
+        "qz_prefill_attention_paged_kv8")
     return out
 
 

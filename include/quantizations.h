@@ -701,8 +701,8 @@ int qz_gemm_4bit_grouped_lora(int nseg, const qz_gemv_segment *segs, const qz_lo
                               int t_stride, const int *slot, int tokens_per_slot, int T, int K, const void *X, int ldx,
                               int dtype, int quant_type, int blocksize, int blocksize2, void *stream);
 
-/* The launch-geometry measurement knobs in effect (QZ_GEMV_WIDE8, QZ_GROUPED_NORM_R, QZ_PAIR_R,
- * QZ_PAIR_WT, QZ_PAIR_PS, QZ_PAIR_WK1, and QZ_GEMM16_SCHED -- the schedule qz_gemm_16bit (default 971, persistent)
+/* The launch-geometry measurement knobs in effect (QZ_GEMV_WIDE8, QZ_GROUPED_NORM_R,
+ * QZ_GROUPED_NORM_NW8, QZ_PAIR_R, QZ_PAIR_WT, QZ_PAIR_PS, QZ_PAIR_WK1, and QZ_GEMM16_SCHED -- the schedule qz_gemm_16bit (default 971, persistent)
  * launches: environment variables read ONCE when the library is loaded) and the
  * device's CU count, as a JSON object written to buf (NUL-terminated when n > the length).
  * Returns the length of the JSON text.  No reference counterpart (measurement bookkeeping). */

@@ -52,6 +52,7 @@ static Knobs read_knobs() {
   k.wide8 = env_int("QZ_GEMV_WIDE8", 1) != 0;
   const int nr = env_int("QZ_GROUPED_NORM_R", 0);
   k.norm_r = (nr == 1 || nr == 2 || nr == 4) ? nr : 0;
+  k.norm_nw8 = env_int("QZ_GROUPED_NORM_NW8", 0) != 0;
   const int pr = env_int("QZ_PAIR_R", 0);
   k.pair_r = (pr == 2 || pr == 3 || pr == 4 || pr == 6 || pr == 8) ? pr : 0;
   k.pair_wt = env_int("QZ_PAIR_WT", 1) != 0;
@@ -257,9 +258,9 @@ extern "C" int qz_gemv_4bit_pair_silu(const qz_gemv_segment *segs, int K, const 
 extern "C" int qz_gemv_knobs(char *buf, int n) {
   char tmp[320];
   const int len = snprintf(tmp, sizeof(tmp),
-                           "{\"QZ_GEMV_WIDE8\": %d, \"QZ_GROUPED_NORM_R\": %d, \"QZ_PAIR_R\": %d, \"QZ_PAIR_WT\": %d, "
-                           "\"QZ_PAIR_PS\": %d, \"QZ_PAIR_WK1\": %d, \"QZ_GEMM16_SCHED\": %d, \"cus\": %d}",
-                           gemv_knobs().wide8, gemv_knobs().norm_r, gemv_knobs().pair_r, gemv_knobs().pair_wt,
+                           "{\"QZ_GEMV_WIDE8\": %d, \"QZ_GROUPED_NORM_R\": %d, \"QZ_GROUPED_NORM_NW8\": %d, \"QZ_PAIR_R\": %d, "
+                           "\"QZ_PAIR_WT\": %d, \"QZ_PAIR_PS\": %d, \"QZ_PAIR_WK1\": %d, \"QZ_GEMM16_SCHED\": %d, \"cus\": %d}",
+                           gemv_knobs().wide8, gemv_knobs().norm_r, gemv_knobs().norm_nw8, gemv_knobs().pair_r, gemv_knobs().pair_wt,
                            gemv_knobs().pair_ps, gemv_knobs().pair_wk1, gemm16_sched(), device_cus());
   if (buf && n > len) memcpy(buf, tmp, (size_t)len + 1);
   return len;
@@ -272,6 +273,7 @@ extern "C" int qz_gemv_set_knob(const char *name, int value) {
   Knobs &k = gemv_knobs();
   if (!strcmp(name, "QZ_GEMV_WIDE8")) k.wide8 = value != 0;
   else if (!strcmp(name, "QZ_GROUPED_NORM_R")) k.norm_r = (value == 1 || value == 2 || value == 4) ? value : 0;
+  else if (!strcmp(name, "QZ_GROUPED_NORM_NW8")) k.norm_nw8 = value != 0;
   else if (!strcmp(name, "QZ_PAIR_R")) k.pair_r = (value == 2 || value == 3 || value == 4 || value == 6 || value == 8) ? value : 0;
   else if (!strcmp(name, "QZ_PAIR_WT")) k.pair_wt = value != 0;
   else if (!strcmp(name, "QZ_PAIR_PS")) k.pair_ps = value;

@@ -514,8 +514,23 @@ template <bool DQ, int DT, int R, bool NOX, bool FS> struct StepLoads {
 
 // Fused pre-norm (NRM): the bit-exact sum of squares of k_rmsnorm (layer_ops.hip): thread t adds
 // the squares of 16-B chunks t, t + 256, ... in element order, then the xor butterfly of the wave
+//
+// fp16: ss + h * h as ONE fused multiply-add per element, the half read in place (v_fma_mix_f32 with
+// op_sel picking the dword's half).  Same bits as fadd(ss, fmul(h, h)): the square of an fp16 value
+// has at most 22 significant bits and lies in [2^-48, 65504^2], so the fp32 product is exact and
+// both forms round ss + h^2 once.  bf16 keeps the separate multiply and add: a bf16 square below
+// 2^-126 is NOT exact in fp32 (|x| < 2^-63), and there the fused form rounds differently on ties.
 template <int DT> __device__ __forceinline__ float norm_chunk_ss(const u32x4 &v, float ss) {
   const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  if constexpr (DT == QZ_DT_F16) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const h2_t h = __builtin_bit_cast(h2_t, w[d]);
+      ss = __builtin_fmaf((float)h.x, (float)h.x, ss);
+      ss = __builtin_fmaf((float)h.y, (float)h.y, ss);
+    }
+    return ss;
+  }
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const uint32_t b = (w[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
@@ -533,6 +548,23 @@ __device__ __forceinline__ float norm_wave_sum(float v) {
 template <int DT> __device__ __forceinline__ u32x4 norm_chunk_apply(const u32x4 &xv, const u32x4 &wv, float rs) {
   const uint32_t xw[4] = {xv.x, xv.y, xv.z, xv.w}, ww[4] = {wv.x, wv.y, wv.z, wv.w};
   uint32_t o[4];
+  if constexpr (DT == QZ_DT_F16) {
+    // Six instructions per element pair, every rounding where torch has it:
+    //  * x * rs in fp32 (v_cvt_f32_f16 of each half in place, v_mul_f32), then ONE packed RNE
+    //    conversion of the pair.  The conversion is an asm statement, so its fp32 operands are
+    //    pinned in registers: hipcc cannot fold the multiply into a single-rounding v_fma_mixlo
+    //    (the known way this code goes wrong, see round_dt in attn_core.h);
+    //  * w * hn as v_pk_mul_f16 on the raw weight dword: the product of two fp16 values is exact in
+    //    fp32 (22 bits, [2^-48, 65504^2]), so fp16(fp32(w * hn)) is the fp16 product rounded once.
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const h2_t xh = __builtin_bit_cast(h2_t, xw[d]);
+      const float x0 = __fmul_rn((float)xh.x, rs), x1 = __fmul_rn((float)xh.y, rs);
+      const h2_t hn = __builtin_bit_cast(h2_t, cvt_pk_f16_rne(x0, x1));
+      o[d] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(h2_t, ww[d]) * hn);
+    }
+    return u32x4{o[0], o[1], o[2], o[3]};
+  }
 #pragma unroll
   for (int d = 0; d < 4; ++d) {
     float r2[2];
@@ -606,7 +638,8 @@ template <bool DQ, int DT, int R, int WK, int NW, bool FS, bool CL, bool WT, boo
 __device__ __forceinline__ void gemv_body(const GemvParams &p_in, const int block, const GemvParams *pair = nullptr,
                                           const LoraOp *lora = nullptr) {
   static_assert(!LORA || (!PAIR && DT != QZ_DT_F32), "adapter operand: single / grouped launches, 16-bit activations");
-  static_assert(!NRM || (NW == 4 && FS && DT != QZ_DT_F32), "fused pre-norm: 4 waves, full steps, 16-bit activations");
+  static_assert(!NRM || ((NW == 4 || (NW == 8 && !PAIR)) && FS && DT != QZ_DT_F32),
+                "fused pre-norm: 4 waves (8: single / grouped launches), full steps, 16-bit activations");
   static_assert(!PAIR || (NW == 4 && WK == 1 && DT != QZ_DT_F32), "pair: 4 waves, WK = 1, 16-bit activations");
   static_assert(!PS || (PAIR && FS), "persistent form: pair launches, full steps");
   static_assert(!TWO || (FS && WK == 1), "two-step form: full steps, whole rows per wave");
@@ -660,20 +693,26 @@ __device__ __forceinline__ void gemv_body(const GemvParams &p_in, const int bloc
   // 1c. NRM: this thread's chunks of x and of the norm weight (L2-resident), ahead of the
   // weights.  The first kNHeld chunks (K <= 4096: all of them) stay in registers across the
   // barrier; later ones are read again after it (registers would cost occupancy)
+  // 8 waves: threads 0-255 form the sum of squares exactly as at 4 waves (chunks t, t + 256, ... of
+  // thread t, s_nss[4]); the apply, which has no order, is split -- chunk round i (chunks 256 i ..
+  // 256 i + 255) goes to the 256-thread half i % 2, so x is normalised once per 512 threads
   constexpr int kNChunks = NRM ? 8 : 1;   // up to 8 x 256 chunks of 8: K <= 16384
   constexpr int kNHeld = NRM ? 2 : 1;
+  constexpr int kNHalves = NRM ? NW / 4 : 1;
   u32x4 nx[kNChunks], nwh[kNHeld];
   const int n_nchunk = p.K >> 3;
+  const int nt = kNHalves == 1 ? (int)threadIdx.x : (int)threadIdx.x & 255;   // thread within its 256-thread half
+  const int nh = kNHalves == 1 ? 0 : wave >> 2;      // the half (wave-uniform)
   if constexpr (NRM) {
 #pragma unroll
     for (int i = 0; i < kNChunks; ++i) {
-      const int c = (int)threadIdx.x + 256 * i;
-      if (c < n_nchunk) nx[i] = reinterpret_cast<const u32x4 *>(p.x)[c];
+      const int c = nt + 256 * i;
+      if (c < n_nchunk && (nh == 0 || i % kNHalves == nh)) nx[i] = reinterpret_cast<const u32x4 *>(p.x)[c];
     }
 #pragma unroll
     for (int i = 0; i < kNHeld; ++i) {
-      const int c = (int)threadIdx.x + 256 * i;
-      if (c < n_nchunk) nwh[i] = reinterpret_cast<const u32x4 *>(p.nw)[c];
+      const int c = nt + 256 * i;
+      if (c < n_nchunk && i % kNHalves == nh) nwh[i] = reinterpret_cast<const u32x4 *>(p.nw)[c];
     }
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -709,12 +748,14 @@ __device__ __forceinline__ void gemv_body(const GemvParams &p_in, const int bloc
   }
   __shared__ float s_nss[NRM ? 4 : 1];
   if constexpr (NRM) {  // sum of squares: per thread in chunk order, per wave by the xor butterfly
-    float ss = 0.0f;
+    if (kNHalves == 1 || nh == 0) {
+      float ss = 0.0f;
 #pragma unroll
-    for (int i = 0; i < kNChunks; ++i)
-      if ((int)threadIdx.x + 256 * i < n_nchunk) ss = norm_chunk_ss<DT>(nx[i], ss);
-    ss = norm_wave_sum(ss);
-    if (lane == 0) s_nss[wave] = ss;
+      for (int i = 0; i < kNChunks; ++i)
+        if (nt + 256 * i < n_nchunk) ss = norm_chunk_ss<DT>(nx[i], ss);
+      ss = norm_wave_sum(ss);
+      if (lane == 0) s_nss[wave] = ss;
+    }
   }
   // output scale: the codebook's (FP4 x12: 1/12; exact NF4: 2^-14), or for a
   // runtime codebook (fp16 x: always exact codes) 2^-S of its in-kernel split
@@ -752,8 +793,8 @@ __device__ __forceinline__ void gemv_body(const GemvParams &p_in, const int bloc
     const float rs = rsqrtf(__fadd_rn(__fmul_rn(tot, 1.0f / (float)p.K), p.eps));
 #pragma unroll
     for (int i = 0; i < kNChunks; ++i) {
-      const int c = (int)threadIdx.x + 256 * i;
-      if (c < n_nchunk) {
+      const int c = nt + 256 * i;
+      if (c < n_nchunk && i % kNHalves == nh) {
         const u32x4 xv = i < kNHeld ? nx[i] : reinterpret_cast<const u32x4 *>(p.x)[c];
         const u32x4 wv = i < kNHeld ? nwh[i < kNHeld ? i : 0] : reinterpret_cast<const u32x4 *>(p.nw)[c];
         *reinterpret_cast<u32x4 *>(s_x + norm_x_off((uint32_t)c)) = norm_chunk_apply<DT>(xv, wv, rs);
@@ -1047,6 +1088,7 @@ __device__ __forceinline__ void gemv_generic_body(const GemvParams &p, int quant
 struct Knobs {
   int wide8;    // QZ_GEMV_WIDE8=0: long-K exact-code GEMVs on 4-wave workgroups (default: 8 waves, 256-B table)
   int norm_r;   // QZ_GROUPED_NORM_R=1|2|4: rows per wave of the normed grouped launch (0 = geometry's)
+  int norm_nw8; // QZ_GROUPED_NORM_NW8=1: the normed grouped launch (exact codes, R = 2) on 8-wave workgroups (default 0)
   int pair_r;   // QZ_PAIR_R=2|3|4|6|8: rows per wave of the pair launch (0 = geometry's)
   int pair_wt;  // QZ_PAIR_WT=0: the persistent pair keeps the 16-copy exact table (default 1)
   int pair_ps;  // QZ_PAIR_PS: 0 = one workgroup per block, 1..8 = workgroups per CU, >= 16 = the grid; -1 = default

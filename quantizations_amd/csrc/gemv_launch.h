@@ -36,6 +36,21 @@ __global__ __launch_bounds__(256) void k_gemv_4bit_grouped(GemvGroup g) {
   gemv_body<DQ, DT, R, WK, 4, FS, CL, false, NRM, false, TWO, false>(seg, b - start);
 }
 
+// The normed grouped launch on 8-wave workgroups with the 256-B-entry table (QZ_GROUPED_NORM_NW8):
+// half as many workgroups, so x is normalised half as often; whole rows per wave, the same bits
+template <bool DQ, int DT, int R, bool CL, bool TWO>
+__global__ __launch_bounds__(512) void k_gemv_4bit_grouped_norm8(GemvGroup g) {
+  const int b = blockIdx.x;
+  int s = 0;
+#pragma unroll
+  for (int i = 1; i < kMaxSeg; ++i)
+    if (i < g.nseg && b >= g.start[i]) s = i;
+  s = __builtin_amdgcn_readfirstlane(s);
+  const GemvParams seg = g.seg[s];   // copied out before load_params launders it (see k_gemv_4bit_grouped)
+  const int start = g.start[s];
+  gemv_body<DQ, DT, R, 1, 8, true, CL, true, true, false, TWO, false>(seg, b - start);
+}
+
 template <bool DQ, int DT, int R, int WK, bool FS, bool CL, bool NRM, bool TWO>
 __global__ __launch_bounds__(256) void k_gemv_4bit_grouped_lora(GemvGroup g, LoraGroup lg) {
   const int b = blockIdx.x;
@@ -258,7 +273,19 @@ static int gemv_grouped_impl(int nseg, const qz_gemv_segment *segs, const qz_lor
   // QZ_GROUPED_NORM_R (knob): rows per wave of the fused pre-norm launch where the geometry keeps
   // whole rows per wave (WK = 1: the same per-row sums)
   if (nw && gemv_knobs().norm_r && WK == 1) R = gemv_knobs().norm_r;
-  const int rows_per_block = R * (4 / WK);
+  int rows_per_block = R * (4 / WK);
+  // QZ_GROUPED_NORM_NW8 (knob, default off: profiles/prenorm_nw8.txt): the fused pre-norm launch with
+  // exact codes at R = 2 on 8-wave workgroups -- half the workgroups, half the norm work -- where the
+  // grid keeps at least 256 of them
+  bool norm8 = false;
+  if constexpr (!LORA) {
+    if (nw && gemv_knobs().norm_nw8 && cl && R == 2 && WK == 1) {
+      long long b8 = 0;
+      for (int i = 0; i < nseg; ++i) b8 += (g.seg[i].M + 2 * 8 - 1) / (2 * 8);
+      norm8 = b8 >= 256;
+      if (norm8) rows_per_block = 2 * 8;
+    }
+  }
   int blocks = 0;
   for (int i = 0; i < nseg; ++i) {
     set_tables(quant_type & ~QZ_EXACT_CODES, lut, cl, dtype, &g.seg[i]);
@@ -305,7 +332,15 @@ static int gemv_grouped_impl(int nseg, const qz_gemv_segment *segs, const qz_lor
     else if constexpr (!LORA) QZ_GR_RW(DQ_, QZ_DT_F32, FS_, false, false);                                          \
     else return QZ_ERR_DTYPE;                                                                                       \
   } while (0)
-  if (nw) {
+  if (norm8) {
+    if constexpr (!LORA) {
+#define QZ_GN8(DQ_, TWO_) \
+  hipLaunchKernelGGL((k_gemv_4bit_grouped_norm8<DQ_, QZ_DT_F16, 2, true, TWO_>), dim3(blocks), dim3(512), lds, s, g)
+      if (dq) { if (two) QZ_GN8(true, true); else QZ_GN8(true, false); }
+      else { if (two) QZ_GN8(false, true); else QZ_GN8(false, false); }
+#undef QZ_GN8
+    }
+  } else if (nw) {
     if (dtype == QZ_DT_F16) {
       if (dq) { if (cl) QZ_GR_RW(true, QZ_DT_F16, true, true, true); else QZ_GR_RW(true, QZ_DT_F16, true, false, true); }
       else { if (cl) QZ_GR_RW(false, QZ_DT_F16, true, true, true); else QZ_GR_RW(false, QZ_DT_F16, true, false, true); }

@@ -602,6 +602,37 @@ int qz_logits_process(void *logits, int dtype, int B, int T, long long V, long l
                       const long long *tok, const float *repetition_penalty, const float *presence_penalty,
                       const float *frequency_penalty, const int *no_repeat_ngram, const long long *min_new_tokens,
                       const long long *prompt_len, const long long *eos, void *work, void *stream);
+/* qz_token_logprobs / qz_logprobs_streams: log-probabilities of 16-bit logits rows (csrc/logprobs.hip;
+ *   two launches for any R: V/2048 x R workgroups read each logit once, one workgroup per row
+ *   finishes; no atomics, no sort, `work` holds 8 + 4 ntop bytes per chunk of 2048 logits).  logits
+ *   [R, V] F16/BF16, row stride `row` >= V.  Per row, with m the row maximum and every operation in
+ *   fp32 (expf / logf): lp(x) = (x - m) - log sum_j exp(x_j - m); a -inf logit has lp = -inf and adds
+ *   nothing to the sum.
+ *   lp: the log-probability of the row's given token (NaN for a token outside [0, V)).
+ *   top_id int32 / top_lp fp32 [.., ntop]: the ntop <= QZ_LOGPROBS_MAX_TOP most likely tokens, value
+ *   descending, then index ascending (-0 equals +0); with V < ntop the tail is id -1, lp -inf;
+ *   ntop = 0 writes no lists (the pointers may be NULL).
+ *   A row that holds a NaN or +inf, or nothing but -inf: lp = NaN, every top_lp = NaN, every top_id = -1.
+ *   A row's outputs depend on that row's V logits alone: not on R, the row's index or the other rows.
+ * qz_token_logprobs: row r's token is ids[r] (int64, device); lp [R], top_id / top_lp [R, ntop].
+ * qz_logprobs_streams: the B*T rows of a step, every address computed on the device.  Row (b, i)
+ *   belongs to column c = pos0[b*pos0_stride] + 1 + i of seq int64 [B, seq_row]; it is live iff
+ *   0 <= c <= pos1[b*pos1_stride] and c < seq_len.  A live row takes its token from seq[b, c] and writes
+ *   lp_tab[b*tab_row + c] and top_id_tab / top_lp_tab[(b*tab_row + c)*ntop + k]; any other row writes
+ *   nothing and its workgroups leave before loading it.
+ * work: qz_logprobs_work_bytes(R, V, ntop) bytes (R = B*T), 16-B aligned, any content.
+ * QZ_ERR_ARG: a NULL logits / ids / seq / pos0 / pos1 / lp / work (or lists with ntop > 0), a
+ *   negative size or ntop, row < V, seq_row or tab_row < seq_len, a stride other than 0 or 1;
+ *   QZ_ERR_DTYPE: not F16/BF16; QZ_ERR_SHAPE: ntop > 20, T > 16, more than 65535 rows, V >= 2^31;
+ *   R, B, T or V of 0 is QZ_OK with nothing launched. */
+#define QZ_LOGPROBS_MAX_TOP 20
+long long qz_logprobs_work_bytes(long long R, long long V, int ntop);
+int qz_token_logprobs(const void *logits, int dtype, long long R, long long V, long long row, const long long *ids,
+                      int ntop, float *lp, int *top_id, float *top_lp, void *work, void *stream);
+int qz_logprobs_streams(const void *logits, int dtype, int B, int T, long long V, long long row, const long long *seq,
+                        long long seq_row, long long seq_len, const long long *pos0, long long pos0_stride,
+                        const long long *pos1, long long pos1_stride, int ntop, float *lp_tab, int *top_id_tab,
+                        float *top_lp_tab, long long tab_row, void *work, void *stream);
 /* qz_gemv_dense: the model's fp16/bf16 lm_head for one decode token (transformers keeps it
  *   unquantised): y[m] = sum_k W[m*K + k] x[k] for m < M, fp32 accumulation, rounded once to
  *   dtype; K in {4096, 8192}, W and x 16-B aligned (else QZ_ERR_SHAPE, nothing launched). */

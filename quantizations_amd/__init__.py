@@ -23,11 +23,13 @@ from .autograd import MatMul4Bit  # noqa: F401
 from .modules import Linear4bit, matmul_4bit  # noqa: F401
 from .generation import (  # noqa: F401
     DecodeSession,
+    GenerateOutput,
     SpeculativeSession,
     StreamSession,
     generate,
     generate_ragged,
     prepare_for_decode,
+    score,
 )
 from . import kv_pages  # noqa: F401
 from .kv_pages import KVPagePool, KVPagesExhausted  # noqa: F401

@@ -143,6 +143,9 @@ SIGNATURES = {
                                       _p, _p, _p],
     "qz_logits_process_work_bytes": [_i, _i, _ll],
     "qz_logits_process": [_p, _i, _i, _i, _ll, _ll, _p, _ll, _ll, _p, _ll, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "qz_logprobs_work_bytes": [_ll, _ll, _i],
+    "qz_token_logprobs": [_p, _i, _ll, _ll, _ll, _p, _i, _p, _p, _p, _p, _p],
+    "qz_logprobs_streams": [_p, _i, _i, _i, _ll, _ll, _p, _ll, _ll, _p, _ll, _p, _ll, _i, _p, _p, _p, _ll, _p, _p],
     "qz_rope_table": [_i, _i, _i, _i, _p, _ll, _ll, _p, _p, _ll, _p, _f, _p, _p, _p],
     "qz_add_rmsnorm": [_p, _p, _i, _ll, _i, _ll, _p, _f, _p, _p, _ll, _p],
     "qz_bench_read_floor": [_p, _ll, _p, _p],
@@ -164,7 +167,8 @@ SIGNATURES = {
 RESTYPES = {"qz_absmax_mean_workspace": _ll, "qz_gemm_4bit_workspace_size": _ll, "qz_gemm_4bit_dgrad_workspace_size": _ll,
             "qz_exchange_bytes": _ll,
             "qz_greedy_step_work_bytes": _ll, "qz_sample_step_work_bytes": _ll,
-            "qz_verify_sample_step_work_bytes": _ll, "qz_logits_process_work_bytes": _ll}
+            "qz_verify_sample_step_work_bytes": _ll, "qz_logits_process_work_bytes": _ll,
+            "qz_logprobs_work_bytes": _ll}
 
 
 def _load():

@@ -16,7 +16,7 @@ stream's history and their own parameters on the device.  One GPU only; no beams
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence, Union
+from typing import NamedTuple, Optional, Sequence, Union
 
 import torch
 
@@ -82,6 +82,42 @@ def _penalty_buffers(sess, batch: int, dev) -> None:
     sess._processing = False   # host knowledge: some processor is on, so the step holds process_logits
 
 
+PROMPT_LOGPROBS_SLAB = 128   # prompt rows per lm_head + token_logprobs call: 128 x V 16-bit logits (31.3 MiB at V = 128256)
+
+
+def _check_logprobs(logprobs, who: str) -> Optional[int]:
+    if logprobs is None:
+        return None
+    if isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= _ops.LOGPROBS_MAX_TOP:
+        raise ValueError(f"{who}: logprobs must be None or an integer in 0..{_ops.LOGPROBS_MAX_TOP}, not {logprobs!r}")
+    return logprobs
+
+
+def _logprob_buffers(sess, logprobs, who: str) -> None:
+    """The log-probability tables of a session opened with `logprobs`, aligned with sess.hist: NaN / -1
+    where there is nothing.  Without it no buffer exists and every hook below returns at once."""
+    sess._lp_n = n = _check_logprobs(logprobs, who)
+    sess.logprobs = sess.top_ids = sess.top_logprobs = sess._pos0 = None
+    if n is None:
+        return
+    B, L, dev = sess.batch, sess.max_len, sess.device
+    sess.logprobs = torch.full((B, L), float("nan"), dtype=torch.float32, device=dev)
+    sess.top_ids = torch.full((B, L, n), -1, dtype=torch.int32, device=dev)
+    sess.top_logprobs = torch.full((B, L, n), float("nan"), dtype=torch.float32, device=dev)
+    sess._pos0 = torch.zeros_like(sess.pos)
+
+
+class GenerateOutput(NamedTuple):
+    """What generate() / generate_ragged() return when `logprobs` is given: tensors for generate(), one
+    tensor per prompt for generate_ragged().  logprobs[.., c] is the log-probability of sequences[.., c]
+    under the model's own distribution (NaN on prompt columns), top_ids / top_logprobs[.., c, :] the most
+    likely tokens there."""
+    sequences: object
+    logprobs: object
+    top_ids: object
+    top_logprobs: object
+
+
 class DecodeSession:
     """One batch of decode streams over `model`: the StaticCache and the static buffers a captured
     step reads and writes -- tok [B, 1], pos [1], hist [B, max_len] (int64), uniform [B, max_len],
@@ -90,13 +126,21 @@ class DecodeSession:
     prompt_len / stop [B] (int64; stop is the EOS min_new_tokens holds back, -1: none).  hist holds
     the sequence itself (prompt, then the picked tokens); pos is the position of `tok`, the newest
     token, which the next step feeds: that step writes its pick to hist[:, pos + 1], drawing it with uniform[:, pos], and advances
-    pos.  prefill() runs the prompt and picks the first new token."""
+    pos.  prefill() runs the prompt and picks the first new token.
 
-    def __init__(self, model, batch: int, max_len: int, *, graph: bool = True):
+    logprobs (None: off -- no buffer, launch or graph node; 0: the chosen tokens; 1..20: that many top
+    entries too): `logprobs` float32 [B, max_len], `top_ids` int32 and `top_logprobs` float32
+    [B, max_len, n], aligned with hist -- entry [b, c] describes token hist[b, c], NaN / -1 where there
+    is none (prompt columns, columns not reached).  The model's own distribution: the log-softmax of
+    the lm_head row before penalties, temperature, top-k and top-p.  One layer_ops.logprobs_streams
+    call follows every pick, inside the captured step; the tokens are those of the session without."""
+
+    def __init__(self, model, batch: int, max_len: int, *, graph: bool = True, logprobs: Optional[int] = None):
         from transformers.cache_utils import StaticCache
 
         if batch < 1 or max_len < 1:
             raise ValueError("DecodeSession: batch and max_len must be positive")
+        _check_logprobs(logprobs, "DecodeSession")
         self.model, self.batch, self.max_len = model, int(batch), int(max_len)
         self.device = next(model.parameters()).device
         self.graph = bool(graph) and self.device.type == "cuda"
@@ -125,6 +169,7 @@ class DecodeSession:
         self._greedy_only = True   # host knowledge: no stream has a temperature > 0
         self._prefilled = False
         self._next = 0   # tokens in hist (host copy of pos + 1)
+        _logprob_buffers(self, logprobs, "DecodeSession")
 
     def set_sampling(self, temperature=None, top_k=None, top_p=None) -> None:
         """Scalars or one value per stream, written in place: the next step, replayed or not, uses
@@ -196,13 +241,43 @@ class DecodeSession:
         else:
             self.uniform.copy_(torch.rand(self.uniform.shape, generator=generator, device=generator.device))
 
+    def _raw_rows(self, logits: torch.Tensor) -> Optional[torch.Tensor]:
+        """In front of a pick, in a session with `logprobs`: snapshot pos and return the rows the
+        log-probabilities are read from -- the logits themselves, or a copy of them when a processing
+        launch is about to rewrite them in place (B T V 16-bit elements, one captured copy)."""
+        if self._lp_n is None:
+            return None
+        self._pos0.copy_(self.pos)
+        return logits.clone() if self._processing else logits
+
+    def _record(self, raw: Optional[torch.Tensor], rows: slice = slice(None), T: int = 1) -> None:
+        """Behind a pick: the log-probabilities of the tokens it emitted (columns pos0 + 1 .. pos of
+        hist), from the model's own rows."""
+        if raw is None:
+            return
+        r, n = rows, self._lp_n
+        _ops.logprobs_streams(raw, self.hist[r], self._pos0[r], self.pos[r], self.logprobs[r],
+                              self.top_ids[r] if n else None, self.top_logprobs[r] if n else None, T)
+
+    def _lp_state(self) -> list:
+        """The tables and the snapshot: a capture's warm-up runs write them, _capture() puts them back."""
+        return [] if self._lp_n is None else [self.logprobs, self.top_ids, self.top_logprobs, self._pos0]
+
+    def _lp_reset(self, b: int) -> None:
+        if self._lp_n is not None:
+            self.logprobs[b] = float("nan")
+            self.top_ids[b] = -1
+            self.top_logprobs[b] = float("nan")
+
     def _pick(self, logits: torch.Tensor) -> None:
+        raw = self._raw_rows(logits)
         self._process(logits)
         if self._greedy_only and logits.is_cuda:
             _ops.greedy_step(logits, self._hist_next, self.pos, self.tok)
         else:
             _ops.sample_step(logits, self._hist_next, self.pos, self.tok, self.temperature, self.top_k, self.top_p,
                              self._uniform_full)
+        self._record(raw)
 
     @torch.inference_mode()
     def prefill(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> None:
@@ -243,7 +318,7 @@ class DecodeSession:
         # two warm-up runs on a side stream, as the benchmark does; they advance the cache lengths,
         # pos, tok and hist, which are put back so that no position is consumed (the keys and values
         # they wrote lie past the restored length: masked now, overwritten by the steps that follow)
-        state = [self.tok, self.pos, self._hist_full] + self._cache_lengths()
+        state = [self.tok, self.pos, self._hist_full] + self._cache_lengths() + self._lp_state()
         saved = [t.clone() for t in state]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -285,7 +360,7 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
              prompt_lookup_num_tokens: Optional[int] = None,
              max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False,
              repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
-             no_repeat_ngram_size=None, min_new_tokens=None) -> torch.Tensor:
+             no_repeat_ngram_size=None, min_new_tokens=None, logprobs: Optional[int] = None):
     """input_ids [B, S] (equal-length prompts) followed by up to max_new_tokens picked tokens per
     stream: greedy, or with do_sample temperature / top_k / top_p (scalars or one per stream; a
     temperature <= 0 keeps that stream greedy) drawn from `generator` (a torch.Generator or a seed).
@@ -301,9 +376,14 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
     repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size, min_new_tokens
     (scalars or one per stream; None: off): set_penalties() -- the processors run inside the step, in
     front of the pick, with or without prompt lookup; min_new_tokens holds eos_token_id back and does
-    nothing without one."""
+    nothing without one.
+    logprobs (None: off; 0: the chosen tokens only; 1..20: that many top entries as well): return a
+    GenerateOutput(sequences, logprobs [B, S + new], top_ids / top_logprobs [B, S + new, n]) aligned
+    with the sequences -- the model's own log-softmax, before penalties, temperature, top-k and top-p;
+    NaN / -1 on the prompt columns and behind a stream's EOS."""
     if input_ids.dim() != 2:
         raise ValueError("generate: input_ids must be [B, S]")
+    _check_logprobs(logprobs, "generate")
     B, S = input_ids.shape
     if prompt_lookup_num_tokens is None and max_matching_ngram_size is not None:
         raise ValueError("generate: max_matching_ngram_size needs prompt_lookup_num_tokens")
@@ -311,14 +391,19 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
         raise ValueError("generate: prompt_lookup_num_tokens verifies drafts against the greedy token; "
                          "do_sample is not supported with it unless prompt_lookup_sampling=True")
     if max_new_tokens < 1:
-        return input_ids.clone()
+        if logprobs is None:
+            return input_ids.clone()
+        dev = input_ids.device
+        return GenerateOutput(input_ids.clone(), torch.full((B, S), float("nan"), device=dev),
+                              torch.full((B, S, logprobs), -1, dtype=torch.int32, device=dev),
+                              torch.full((B, S, logprobs), float("nan"), device=dev))
     penalties = _given_penalties(repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size,
                                  min_new_tokens)
     if prompt_lookup_num_tokens is not None:
         sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator) if do_sample else None
         return _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attention_mask, graph,
-                                     prompt_lookup_num_tokens, max_matching_ngram_size, sampling, penalties)
-    sess = DecodeSession(model, B, S + max_new_tokens, graph=graph)
+                                     prompt_lookup_num_tokens, max_matching_ngram_size, sampling, penalties, logprobs)
+    sess = DecodeSession(model, B, S + max_new_tokens, graph=graph, logprobs=logprobs)
     if penalties:
         sess.set_penalties(**penalties)
         if eos_token_id is not None:
@@ -336,11 +421,17 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
             if bool((new == eos_token_id).any(1).all()):
                 break
     out = sess.hist[:, :S + n].clone()
+    tabs = None if logprobs is None else [t[:, :S + n].clone() for t in sess._lp_state()[:3]]
     if eos_token_id is not None:
         new = out[:, S:]
         ended = (new == eos_token_id).cumsum(1) > 0
+        if tabs is not None:      # behind a stream's first EOS nothing was emitted
+            behind = torch.cat((torch.zeros_like(ended[:, :1]), ended[:, :-1]), 1)
+            tabs[0][:, S:][behind] = float("nan")
+            tabs[1][:, S:][behind] = -1
+            tabs[2][:, S:][behind] = float("nan")
         new[ended] = eos_token_id
-    return out
+    return out if tabs is None else GenerateOutput(out, *tabs)
 
 
 def _given_penalties(repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size,
@@ -455,11 +546,26 @@ class StreamSession:
 
     kv_dtype (None: the model's 16-bit dtype; "fp8" needs kv_pages): the pages hold kv8 rows, D E4M3
     codes and one power-of-two scale byte per row, in (D + 1) / 2D of the bytes; everything above works
-    unchanged, and a step scores the new token as every later step reads it back."""
+    unchanged, and a step scores the new token as every later step reads it back.
+
+    logprobs: DecodeSession's tables, per stream: a stream that is not live has nothing written, admit(b)
+    resets row b's columns to NaN / -1, fork(src, dst) copies them, extend() keeps them.
+    prompt_logprobs=True (needs prefill_chunk and logprobs): the windows of prefill() / admit() / extend()
+    fill the prompt columns 1..S-1 too, the lm_head and layer_ops.token_logprobs over
+    PROMPT_LOGPROBS_SLAB window rows at a time (the logits scratch is that many rows x V, never B S x V).
+    Column 0 stays NaN, and so do the columns of pages mapped from the prefix cache (no forward ran
+    there) and the first column behind them."""
 
     def __init__(self, model, batch: int, max_len: int, *, graph: bool = True, prefill_chunk: Optional[int] = None,
-                 kv_pages: Optional[int] = None, prefix_cache: bool = False, kv_dtype: Optional[str] = None):
+                 kv_pages: Optional[int] = None, prefix_cache: bool = False, kv_dtype: Optional[str] = None,
+                 logprobs: Optional[int] = None, prompt_logprobs: bool = False):
         _check_kv_dtype(kv_dtype, "StreamSession", kv_pages)
+        _check_logprobs(logprobs, "StreamSession")
+        if prompt_logprobs and prefill_chunk is None:
+            raise ValueError("StreamSession: prompt_logprobs needs prefill_chunk (the prompt's rows are scored "
+                             "window by window)")
+        if prompt_logprobs and logprobs is None:
+            raise ValueError("StreamSession: prompt_logprobs fills the tables `logprobs` opens; give logprobs too")
         if batch < 1 or max_len < 2:
             raise ValueError("StreamSession: batch must be positive and max_len at least 2")
         if prefill_chunk is not None and int(prefill_chunk) < 1:
@@ -512,14 +618,21 @@ class StreamSession:
         self._graph = None
         self._greedy_only = True
         self._prefilled = False
+        self.prompt_logprobs = bool(prompt_logprobs)
+        _logprob_buffers(self, logprobs, "StreamSession")
 
     set_sampling = DecodeSession.set_sampling
     set_penalties = DecodeSession.set_penalties
     _process = DecodeSession._process
     seed = DecodeSession.seed
+    _raw_rows = DecodeSession._raw_rows
+    _record = DecodeSession._record
+    _lp_state = DecodeSession._lp_state
+    _lp_reset = DecodeSession._lp_reset
 
     def _pick(self, logits: torch.Tensor, rows: slice = slice(None)) -> None:
         r = rows
+        raw = self._raw_rows(logits)
         self._process(logits, r)
         if self._greedy_only:
             _ops.greedy_step_streams(logits, self._hist_next[r], self.pos[r], self.live[r], self.stop[r],
@@ -528,6 +641,7 @@ class StreamSession:
             _ops.sample_step_streams(logits, self._hist_next[r], self.pos[r], self.live[r], self.stop[r],
                                      self.limit[r], self.tok[r], self.temperature[r], self.top_k[r], self.top_p[r],
                                      self._uniform_full[r])
+        self._record(raw, r)
 
     def _limit_of(self, length: int, max_new_tokens: Optional[int]) -> int:
         room = self.max_len - length
@@ -568,10 +682,38 @@ class StreamSession:
             h = decoder(input_ids=ids[:, s0:s0 + T], past_key_values=self.cache, position_ids=pids,
                         attention_mask=one.expand(nb, 1, T, self.max_len), use_cache=True,
                         _qz_prefill=(pos, length, int(row0)), **self._extra).last_hidden_state
+            if self.prompt_logprobs:
+                self._score_window(h, ids, counts, row0, start, s0, T)
             idx = n - 1 - s0
             mine = h[rows, idx.clamp(0, T - 1)]
             last = mine if last is None else torch.where(((idx >= 0) & (idx < T))[:, None], mine, last)
         return last
+
+    def _score_window(self, h: torch.Tensor, ids: torch.Tensor, counts, row0: int, start: int, s0: int, T: int) -> None:
+        """prompt_logprobs: the window's rows (r, j) whose token ids[r, s0 + j] has a prompt token behind
+        it score that token -- lm_head and token_logprobs over PROMPT_LOGPROBS_SLAB rows at a time, so
+        the logits scratch is slab x V however long the prompts are -- into column start + s0 + j + 1 of
+        stream row0 + r's tables.  (The last prompt token's row is the pick's.)"""
+        rr, jj = [], []
+        for r, cnt in enumerate(counts):
+            k = min(T, int(cnt) - 1 - s0)
+            if k > 0:
+                rr += [r] * k
+                jj += range(k)
+        if not rr:
+            return
+        dev, n = self.device, self._lp_n
+        rt, jt = torch.tensor(rr, device=dev), torch.tensor(jj, device=dev)
+        hid, nxt = h[rt, jt], ids[rt, s0 + jt + 1].contiguous()
+        srow, cols = row0 + rt, start + s0 + jt + 1
+        head = self.model.get_output_embeddings()
+        for a in range(0, len(rr), PROMPT_LOGPROBS_SLAB):
+            z = slice(a, a + PROMPT_LOGPROBS_SLAB)
+            lp, ti, tl = _ops.token_logprobs(head(hid[z].unsqueeze(0))[0], nxt[z], n)
+            self.logprobs[srow[z], cols[z]] = lp
+            if n:
+                self.top_ids[srow[z], cols[z]] = ti
+                self.top_logprobs[srow[z], cols[z]] = tl
 
     def _slots(self, limit: int) -> int:
         """Cache slots a stream with this limit may write: one per position up to the limit, where a
@@ -680,6 +822,7 @@ class StreamSession:
                 hit = self.pages.lookup(ids[0], salt) if salt is not False else []
                 self.pages.assign(b, hit, self._slots(limit))
                 start = _ops.KV_PAGE * len(hit)
+            self._lp_reset(b)
             hidden = self._windows(ids[:, start:], [S - start], b, start)
             self._set_stream(b, ids[0], 0, S, stop, limit)
             self._pick(self._head(hidden), slice(b, b + 1))
@@ -696,6 +839,7 @@ class StreamSession:
             mine.keys[b, :, :S].copy_(theirs.keys[0, :, :S])
             mine.values[b, :, :S].copy_(theirs.values[0, :, :S])
         self._hist_full[b, :S] = ids[0]
+        self._lp_reset(b)
         self.pos[b] = S - 1
         self.prompt_len[b] = S
         self.stop[b] = -1 if stop is None else int(stop)
@@ -786,6 +930,8 @@ class StreamSession:
                 layer.keys[pair[1]].copy_(layer.keys[pair[0]])
                 layer.values[pair[1]].copy_(layer.values[pair[0]])
         self._hist_full[dst].copy_(self._hist_full[src])
+        for t in self._lp_state()[:3]:
+            t[dst].copy_(t[src])
         self.tok[dst].copy_(self.tok[src])
         if hasattr(self, "pos_ids"):
             self.pos_ids[dst].copy_(self.pos_ids[src])
@@ -809,7 +955,7 @@ class StreamSession:
 
     def _step_state(self) -> list:
         """What a step writes besides the cache: _capture() puts it back after its warm-up runs."""
-        return [self.tok, self.pos, self.live, self._hist_full]
+        return [self.tok, self.pos, self.live, self._hist_full] + self._lp_state()
 
     def _capture(self) -> None:
         # two warm-up runs on a side stream, then the capture; each advances the live streams, which
@@ -891,7 +1037,8 @@ class SpeculativeSession(StreamSession):
 
     def __init__(self, model, batch: int, max_len: int, *, draft_tokens: int = 3, ngram: int = 3, graph: bool = True,
                  sample: bool = False, prefill_chunk: Optional[int] = None, kv_pages: Optional[int] = None,
-                 prefix_cache: bool = False, kv_dtype: Optional[str] = None):
+                 prefix_cache: bool = False, kv_dtype: Optional[str] = None, logprobs: Optional[int] = None,
+                 prompt_logprobs: bool = False):
         from .core import MT_MAX_TOKENS
 
         if int(draft_tokens) < 1:
@@ -903,7 +1050,8 @@ class SpeculativeSession(StreamSession):
             raise ValueError(f"SpeculativeSession: batch * (draft_tokens + 1) = {batch * T} rows per step, the "
                              f"multi-token kernels take {MT_MAX_TOKENS}")
         super().__init__(model, batch, max_len, graph=graph, prefill_chunk=prefill_chunk, kv_pages=kv_pages,
-                         prefix_cache=prefix_cache, kv_dtype=kv_dtype)
+                         prefix_cache=prefix_cache, kv_dtype=kv_dtype, logprobs=logprobs,
+                         prompt_logprobs=prompt_logprobs)
         dev = self.device
         self.T, self.ngram, self.sample = T, int(ngram), bool(sample)
         self.tok = torch.zeros((batch, T), dtype=torch.int64, device=dev)
@@ -929,6 +1077,7 @@ class SpeculativeSession(StreamSession):
         # prefill() and admit(): one row of logits per stream, the plain pick, then drafts for everyone
         # (a stream whose state did not change gets the drafts it had, or others: they are hints)
         r = rows
+        raw = self._raw_rows(logits)
         self._process(logits, r)
         first = self.tok[r, :1].contiguous()
         if self._greedy_only:
@@ -939,12 +1088,14 @@ class SpeculativeSession(StreamSession):
                                      self.limit[r], first, self.temperature[r], self.top_k[r], self.top_p[r],
                                      self._uniform_full[r])
         self.tok[r, :1] = first
+        self._record(raw, r)
         self._draft()
 
     def _step(self) -> None:
         lo = self.model(input_ids=self.tok, past_key_values=self.cache, position_ids=self.pos_ids,
                         attention_mask=self._mask, use_cache=True, _qz_verify_pos=self.pos, **self._extra).logits
         lo = lo.reshape(self.batch * self.T, -1)
+        raw = self._raw_rows(lo)
         self._process(lo, tok=self.tok)    # row i sees the drafts 1..i it was fed after
         if self._greedy_only:
             _ops.verify_step_streams(lo, self._hist_next, self.pos, self.live, self.stop, self.limit, self.tok,
@@ -953,6 +1104,7 @@ class SpeculativeSession(StreamSession):
             _ops.verify_sample_step_streams(lo, self._hist_next, self.pos, self.live, self.stop, self.limit, self.tok,
                                             self.accepted, self.temperature, self.top_k, self.top_p,
                                             self._uniform_full)
+        self._record(raw, T=self.T)        # the accepted rows: columns pos0 + 1 .. pos
         self._tokens.add_(self.accepted)
         self._steps.add_(self.accepted.ne(0))
         self._draft()
@@ -969,14 +1121,14 @@ class SpeculativeSession(StreamSession):
 def _speculative_session(model, batch: int, max_len: int, prompt_lookup_num_tokens, max_matching_ngram_size,
                          do_sample: bool, graph: bool, who: str, sampling: bool = False,
                          prefill_chunk: Optional[int] = None, kv_pages: Optional[int] = None,
-                         kv_dtype: Optional[str] = None) -> SpeculativeSession:
+                         kv_dtype: Optional[str] = None, logprobs: Optional[int] = None) -> SpeculativeSession:
     if do_sample and not sampling:
         raise ValueError(f"{who}: prompt_lookup_num_tokens verifies drafts against the greedy token; "
                          "do_sample is not supported with it unless prompt_lookup_sampling=True")
     n = PROMPT_LOOKUP_NGRAM if max_matching_ngram_size is None else int(max_matching_ngram_size)
     return SpeculativeSession(model, batch, max_len, draft_tokens=int(prompt_lookup_num_tokens), ngram=n, graph=graph,
                               sample=bool(do_sample and sampling), prefill_chunk=prefill_chunk, kv_pages=kv_pages,
-                              kv_dtype=kv_dtype)
+                              kv_dtype=kv_dtype, logprobs=logprobs)
 
 
 def _run_speculative(sess: SpeculativeSession, max_new_tokens: int) -> None:
@@ -989,7 +1141,7 @@ def _run_speculative(sess: SpeculativeSession, max_new_tokens: int) -> None:
 
 def _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attention_mask, graph,
                           prompt_lookup_num_tokens, max_matching_ngram_size, sampling=None,
-                          penalties=None) -> torch.Tensor:
+                          penalties=None, logprobs=None):
     """generate()'s result from a SpeculativeSession: every stream runs to its EOS or to max_new_tokens,
     then the rows are laid out as the plain loop leaves them -- S + n columns, n the first multiple of
     STOP_CHECK_EVERY by which every stream had its EOS (max_new_tokens if there is none), each
@@ -999,7 +1151,7 @@ def _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attent
         raise ValueError("generate: padded prompts are not supported (attention_mask holds a zero)")
     B, S = input_ids.shape
     sess = _speculative_session(model, B, S + max_new_tokens, prompt_lookup_num_tokens, max_matching_ngram_size,
-                                sampling is not None, graph, "generate", sampling is not None)
+                                sampling is not None, graph, "generate", sampling is not None, logprobs=logprobs)
     if sampling is not None:
         sess.set_sampling(temperature=sampling["temperature"], top_k=sampling["top_k"], top_p=sampling["top_p"])
         sess.seed(sampling["generator"])
@@ -1016,7 +1168,10 @@ def _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attent
     out = torch.full((B, S + n), fill, dtype=torch.int64, device=sess.device)
     for b, s in enumerate(seqs):
         out[b, :s.numel()] = s
-    return out
+    if logprobs is None:
+        return out
+    # a stream that stopped wrote nothing more: the tables' columns behind its EOS are still NaN / -1
+    return GenerateOutput(out, *(t[:, :S + n].clone() for t in sess._lp_state()[:3]))
 
 
 @torch.inference_mode()
@@ -1027,7 +1182,7 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
                     max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False,
                     repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
                     no_repeat_ngram_size=None, min_new_tokens=None, prefill_chunk: Optional[int] = None,
-                    kv_pages: Optional[int] = None, kv_dtype: Optional[str] = None) -> list:
+                    kv_pages: Optional[int] = None, kv_dtype: Optional[str] = None, logprobs: Optional[int] = None):
     """generate() for prompts of different lengths: `prompts` are 1-D int64 tensors; returns one 1-D
     int64 tensor per prompt on the model's device, the prompt followed by up to max_new_tokens picked
     tokens of its own, ending with eos_token_id if the stream picked it.  A stream that stopped writes
@@ -1043,7 +1198,10 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     prompts through layer_ops.prefill_attention in windows of that many tokens.
     kv_pages: the session's: that many pages of 128 positions per layer in place of a cache row of
     Smax + max_new_tokens positions per prompt (needs prefill_chunk).
-    kv_dtype: the session's: "fp8" keeps the pages as kv8 rows (needs kv_pages)."""
+    kv_dtype: the session's: "fp8" keeps the pages as kv8 rows (needs kv_pages).
+    logprobs: as generate() takes it; the GenerateOutput's fields are lists with one tensor per prompt,
+    each cut to that prompt's sequence."""
+    _check_logprobs(logprobs, "generate_ragged")
     prompts = list(prompts)
     if not prompts or any((not isinstance(p, torch.Tensor)) or p.dim() != 1 or p.numel() < 1 for p in prompts):
         raise ValueError("generate_ragged: prompts must be a non-empty sequence of non-empty 1-D tensors")
@@ -1054,12 +1212,12 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     if prompt_lookup_num_tokens is not None:
         sess = _speculative_session(model, B, Smax + max_new_tokens, prompt_lookup_num_tokens,
                                     max_matching_ngram_size, do_sample, graph, "generate_ragged",
-                                    prompt_lookup_sampling, prefill_chunk, kv_pages, kv_dtype)
+                                    prompt_lookup_sampling, prefill_chunk, kv_pages, kv_dtype, logprobs)
     elif max_matching_ngram_size is not None:
         raise ValueError("generate_ragged: max_matching_ngram_size needs prompt_lookup_num_tokens")
     else:
         sess = StreamSession(model, B, Smax + max_new_tokens, graph=graph, prefill_chunk=prefill_chunk,
-                             kv_pages=kv_pages, kv_dtype=kv_dtype)
+                             kv_pages=kv_pages, kv_dtype=kv_dtype, logprobs=logprobs)
     if do_sample:
         sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
         sess.seed(generator)
@@ -1073,11 +1231,51 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     sess.prefill(ids, lens, stop=eos_token_id, max_new_tokens=max_new_tokens)
     if isinstance(sess, SpeculativeSession):
         _run_speculative(sess, max_new_tokens)
-        return sess.sequences()
+        return _ragged_output(sess)
     n = 1
     while n < max_new_tokens:
         sess.step()
         n += 1
         if eos_token_id is not None and n % STOP_CHECK_EVERY == 0 and not bool(sess.alive().any()):
             break
-    return sess.sequences()
+    return _ragged_output(sess)
+
+
+def _ragged_output(sess):
+    """sequences(), and with `logprobs` the tables' rows cut to them."""
+    seqs = sess.sequences()
+    if sess._lp_n is None:
+        return seqs
+    return GenerateOutput(seqs, *([t[b, :s.numel()].clone() for b, s in enumerate(seqs)] for t in sess._lp_state()[:3]))
+
+
+@torch.inference_mode()
+def score(model, prompts: Sequence[torch.Tensor], *, top_logprobs: int = 0, prefill_chunk: int = 512) -> list:
+    """Log-probabilities of given texts: `prompts` are 1-D int64 tensors; returns one float32 tensor t
+    per prompt on the model's device with t[c] = log p(token_c | tokens_<c) under the model (t[0] is
+    NaN: nothing precedes the first token), so (-t[1:].mean()).exp() is the prompt's perplexity.  The
+    prompts run through a StreamSession(prefill_chunk=..., prompt_logprobs=True) in windows of
+    prefill_chunk tokens, the lm_head over PROMPT_LOGPROBS_SLAB rows at a time; no decode step is
+    captured or run.  top_logprobs = n in 1..20: each entry is (t, top_ids [S, n], top_logprobs [S, n])
+    instead, the n most likely tokens at every column.  One GPU and prepare_for_decode()'s layout."""
+    _single_gpu_prepared(model, "score")
+    n = top_logprobs
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= _ops.LOGPROBS_MAX_TOP:
+        raise ValueError(f"score: top_logprobs must be an integer in 0..{_ops.LOGPROBS_MAX_TOP}, not {n!r}")
+    prompts = list(prompts)
+    if not prompts or any((not isinstance(p, torch.Tensor)) or p.dim() != 1 or p.numel() < 1 for p in prompts):
+        raise ValueError("score: prompts must be a non-empty sequence of non-empty 1-D tensors")
+    if prefill_chunk is None or int(prefill_chunk) < 1:
+        raise ValueError("score: prefill_chunk must be at least 1")
+    lens = [p.numel() for p in prompts]
+    B, Smax = len(prompts), max(lens)
+    sess = StreamSession(model, B, Smax + 1, graph=False, prefill_chunk=int(prefill_chunk), logprobs=n,
+                         prompt_logprobs=True)
+    ids = torch.zeros((B, Smax), dtype=torch.int64, device=sess.device)
+    for b, p in enumerate(prompts):
+        ids[b, :lens[b]] = p.to(sess.device)
+    sess.prefill(ids, lens, max_new_tokens=1)
+    if not n:
+        return [sess.logprobs[b, :S].clone() for b, S in enumerate(lens)]
+    return [(sess.logprobs[b, :S].clone(), sess.top_ids[b, :S].clone(), sess.top_logprobs[b, :S].clone())
+            for b, S in enumerate(lens)]

@@ -1284,6 +1284,140 @@ def process_logits(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, 
         _lib.stream_of(logits)), "qz_logits_process")
 
 
+LOGPROBS_MAX_TOP = 20   # QZ_LOGPROBS_MAX_TOP
+
+
+def token_logprobs_supported(logits: torch.Tensor) -> bool:
+    """What qz_token_logprobs / qz_logprobs_streams take: fp16 / bf16 logits [R, V] on the GPU with unit
+    element stride and a row stride of at least V, at most 65535 rows.  Metadata only."""
+    return (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype in (torch.float16, torch.bfloat16)
+            and logits.dim() == 2 and logits.stride(-1) == 1 and logits.stride(0) >= logits.shape[1]
+            and logits.shape[0] <= 65535 and logits.shape[1] < 2 ** 31)
+
+
+def _token_logprobs_composed(logits, ids, top):
+    """qz_token_logprobs' rules in torch ops: fp32 log_softmax, a stable descending sort for the lists."""
+    R, V = logits.shape
+    dev = logits.device
+    z = logits.float()
+    nan = torch.full((), float("nan"), device=dev)
+    bad = torch.isnan(z).any(1) | (z == float("inf")).any(1) | (z.max(1).values == float("-inf"))
+    lsm = torch.where(bad[:, None], nan, torch.log_softmax(z, -1))
+    inside = (ids >= 0) & (ids < V)
+    lp = torch.where(inside, lsm.gather(1, ids.clamp(0, V - 1)[:, None])[:, 0], nan)
+    top_id = torch.full((R, top), -1, dtype=torch.int32, device=dev)
+    top_lp = torch.full((R, top), float("-inf"), dtype=torch.float32, device=dev)
+    k = min(top, V)
+    if k:
+        order = torch.sort(z, dim=1, descending=True, stable=True).indices[:, :k]
+        top_id[:, :k] = order.to(torch.int32)
+        top_lp[:, :k] = lsm.gather(1, order)
+    if top:
+        top_id[bad] = -1
+        top_lp[bad] = nan
+    return lp, top_id, top_lp
+
+
+def _check_logprobs_logits(name, logits, top):
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.stride(-1) != 1:
+        raise ValueError(f"{name}: logits must be [R, V] with unit element stride")
+    if not isinstance(top, int) or isinstance(top, bool) or not 0 <= top <= LOGPROBS_MAX_TOP:
+        raise ValueError(f"{name}: top must be an integer in 0..{LOGPROBS_MAX_TOP}")
+
+
+def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, top: int = 0, *, composed: bool = False):
+    """Log-probabilities of logits rows (qz_token_logprobs; include/quantizations.h states the rules).
+    logits [R, V] (unit element stride), ids int64 [R] on the logits' device.  Returns (lp float32 [R]:
+    the log-softmax of row r at ids[r], NaN for an id outside [0, V); top_id int32 [R, top] and top_lp
+    float32 [R, top]: the `top` <= LOGPROBS_MAX_TOP most likely tokens of each row, value descending then
+    index ascending, padded with -1 / -inf when V < top).  A row holding a NaN or +inf, or nothing but
+    -inf, is NaN / -1 throughout.  fp32 or CPU logits (token_logprobs_supported is false), or
+    composed=True, take the same rules in torch ops (fp32 log_softmax, a stable sort)."""
+    _check_logprobs_logits("token_logprobs", logits, top)
+    R, V = logits.shape
+    if (not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.device != logits.device
+            or ids.shape != (R,) or not ids.is_contiguous()):
+        raise ValueError("token_logprobs: ids must be contiguous int64 [R] on the logits' device")
+    dev = logits.device
+    if not (R and V):
+        return (torch.full((R,), float("nan"), dtype=torch.float32, device=dev),
+                torch.full((R, top), -1, dtype=torch.int32, device=dev),
+                torch.full((R, top), float("-inf"), dtype=torch.float32, device=dev))
+    if composed or not token_logprobs_supported(logits):
+        return _token_logprobs_composed(logits, ids, top)
+    lp = torch.empty(R, dtype=torch.float32, device=dev)
+    top_id = torch.empty((R, top), dtype=torch.int32, device=dev)
+    top_lp = torch.empty((R, top), dtype=torch.float32, device=dev)
+    work = torch.empty(_lib.lib.qz_logprobs_work_bytes(R, V, top), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib.qz_token_logprobs(
+        logits.data_ptr(), _lib.dtype_code(logits.dtype), R, V, logits.stride(0), ids.data_ptr(), top, lp.data_ptr(),
+        top_id.data_ptr() if top else 0, top_lp.data_ptr() if top else 0, work.data_ptr(), _lib.stream_of(logits)),
+        "qz_token_logprobs")
+    return lp, top_id, top_lp
+
+
+def logprobs_streams(logits: torch.Tensor, seq: torch.Tensor, pos0: torch.Tensor, pos1: torch.Tensor,
+                     lp_tab: torch.Tensor, top_id_tab: Optional[torch.Tensor] = None,
+                     top_lp_tab: Optional[torch.Tensor] = None, T: int = 1, *, composed: bool = False) -> None:
+    """The log-probabilities of the tokens a step emitted, written into a session's tables
+    (qz_logprobs_streams).  logits [B*T, V]; seq int64 [B, L] (unit element stride) is the sequence
+    itself; pos0 / pos1 int64 [1] (one position for all) or [B]: the streams' positions before and after
+    the pick.  Row (b, i) describes column c = pos0[b] + 1 + i and is live iff 0 <= c <= pos1[b] and
+    c < L: then lp_tab[b, c] (float32 [B, >= L]) is the log-probability of seq[b, c] under the row, and
+    top_id_tab[b, c, :] (int32) / top_lp_tab[b, c, :] (float32), [B, as lp_tab, n] with n <=
+    LOGPROBS_MAX_TOP, its n most likely tokens (both None: no lists).  Any other row writes nothing.
+    Every address is computed on the device, so a captured call follows the streams.  fp32 or CPU
+    logits, or composed=True, take the same rules in torch ops (not capturable)."""
+    n = 0 if top_id_tab is None else int(top_id_tab.shape[-1])
+    _check_logprobs_logits("logprobs_streams", logits, n)
+    dev = logits.device
+    if (not isinstance(seq, torch.Tensor) or seq.dtype != torch.int64 or seq.device != dev or seq.dim() != 2
+            or (seq.shape[1] > 1 and seq.stride(1) != 1) or seq.stride(0) < seq.shape[1]):
+        raise ValueError("logprobs_streams: seq must be int64 [B, L] with unit element stride on the logits' device")
+    B, L = seq.shape
+    if not 1 <= T <= VERIFY_MAX_T:
+        raise ValueError(f"logprobs_streams: T must be in 1..{VERIFY_MAX_T}")
+    R, V = logits.shape
+    if R != B * T:
+        raise ValueError("logprobs_streams: logits must be [B*T, V]")
+    for t, what in ((pos0, "pos0"), (pos1, "pos1")):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.device != dev or not t.is_contiguous()
+                or t.numel() not in (1, B)):
+            raise ValueError(f"logprobs_streams: {what} must be contiguous int64 [1] or [B] on the logits' device")
+    if (not isinstance(lp_tab, torch.Tensor) or lp_tab.dtype != torch.float32 or lp_tab.device != dev
+            or lp_tab.dim() != 2 or lp_tab.shape[0] != B or lp_tab.shape[1] < L or not lp_tab.is_contiguous()):
+        raise ValueError("logprobs_streams: lp_tab must be contiguous float32 [B, >= L] on the logits' device")
+    if (top_id_tab is None) != (top_lp_tab is None):
+        raise ValueError("logprobs_streams: top_id_tab and top_lp_tab go together")
+    for t, dt, what in ((top_id_tab, torch.int32, "top_id_tab"), (top_lp_tab, torch.float32, "top_lp_tab")):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != dev
+                              or t.shape != (B, lp_tab.shape[1], n) or not t.is_contiguous()):
+            raise ValueError(f"logprobs_streams: {what} must be contiguous {dt} [B, {lp_tab.shape[1]}, n]")
+    if not (B and V and L):
+        return
+    if composed or not token_logprobs_supported(logits):
+        b = torch.arange(B, device=dev).repeat_interleave(T)
+        i = torch.arange(T, device=dev).repeat(B)
+        p0 = (pos0.expand(B) if pos0.numel() == 1 else pos0)[b]
+        p1 = (pos1.expand(B) if pos1.numel() == 1 else pos1)[b]
+        c = p0 + 1 + i
+        live = (c >= 0) & (c <= p1) & (c < L)
+        cc = c.clamp(0, L - 1)
+        lp, ti, tl = _token_logprobs_composed(logits, seq[b, cc], n)
+        lp_tab[b[live], cc[live]] = lp[live]
+        if n:
+            top_id_tab[b[live], cc[live]] = ti[live]
+            top_lp_tab[b[live], cc[live]] = tl[live]
+        return
+    work = torch.empty(_lib.lib.qz_logprobs_work_bytes(R, V, n), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib.qz_logprobs_streams(
+        logits.data_ptr(), _lib.dtype_code(logits.dtype), B, T, V, logits.stride(0), seq.data_ptr(), seq.stride(0), L,
+        pos0.data_ptr(), 0 if pos0.numel() == 1 and B > 1 else 1, pos1.data_ptr(),
+        0 if pos1.numel() == 1 and B > 1 else 1, n, lp_tab.data_ptr(), _lib.ptr(top_id_tab) if n else 0,
+        _lib.ptr(top_lp_tab) if n else 0, lp_tab.shape[1], work.data_ptr(), _lib.stream_of(logits)),
+        "qz_logprobs_streams")
+
+
 def ngram_draft_reference(seq, tok0: int, p: int, T: int, ngram_max: int) -> list:
     """The drafter's rule on host integers: seq[0..p] is the stream's history (seq[p] the newest
     token), the result its T - 1 drafts."""

@@ -438,7 +438,7 @@ int qz_prefill_attention_paged(int dtype, int B, int T, int Hq, int Hkv, int D, 
                                const int *table, long long table_row, const long long *pos, const long long *len,
                                void *out, long long out_row, float scale, void *stream);
 
-/* FP8 paged KV cache, "kv8" (csrc/paged_attn_kv8.hip): the three paged launches over byte pools.
+/* FP8 paged KV cache, "kv8" (csrc/paged_attn.hip): the three paged launches over byte pools.
  *   A cache row (one position of one kv head, D elements of K or of V) is D OCP E4M3 codes and one
  *   scale byte s = e + 127 that stands for 2^e: e is the smallest exponent with absmax*2^-e <= 448,
  *   not below e_min (-15 for fp16, -124 for bf16); code i is x_i*2^-e rounded to nearest even.  A row

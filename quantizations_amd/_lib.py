@@ -106,12 +106,6 @@ SIGNATURES = {
     "qz_prefill_attention_paged": [_i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p,
                                    _ll, _p, _p, _p, _ll, _f, _p],
     "qz_kv8_page_head_bytes": [_i],
-    "qz_decode_attention_paged_kv8": [_i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p,
-                                      _ll, _p, _p, _ll, _p, _f, _p],
-    "qz_decode_attention_verify_paged_kv8": [_i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p,
-                                             _p, _p, _ll, _p, _p, _ll, _p, _f, _p],
-    "qz_prefill_attention_paged_kv8": [_i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p,
-                                       _p, _ll, _p, _p, _p, _ll, _f, _p],
     "qz_verify_step_streams": [_p, _i, _i, _i, _ll, _ll, _p, _ll, _ll, _p, _p, _p, _p, _p, _p, _p, _p],
     "qz_ngram_draft": [_i, _i, _i, _p, _ll, _ll, _p, _p, _p, _p],
     "qz_greedy_step_streams": [_p, _i, _i, _ll, _ll, _p, _ll, _ll, _p, _p, _p, _p, _p, _p, _p],
@@ -164,6 +158,9 @@ SIGNATURES = {
     "qz_gemv_set_knob": [ctypes.c_char_p, _i],
     "qz_version": [],
 }
+# the kv8 paged launches take their 16-bit twins' operand lists (the pools are bytes behind the same pointers)
+for _name in ("qz_decode_attention_paged", "qz_decode_attention_verify_paged", "qz_prefill_attention_paged"):
+    SIGNATURES[_name + "_kv8"] = SIGNATURES[_name]
 RESTYPES = {"qz_absmax_mean_workspace": _ll, "qz_gemm_4bit_workspace_size": _ll, "qz_gemm_4bit_dgrad_workspace_size": _ll,
             "qz_exchange_bytes": _ll,
             "qz_greedy_step_work_bytes": _ll, "qz_sample_step_work_bytes": _ll,

@@ -16,6 +16,7 @@
 // bit-identical k), scores and probabilities stay fp32 (SDPA's flash kernel rounds the
 // probabilities to the storage dtype before P V; this kernel does not), output rounded once.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace qz {
@@ -86,8 +87,8 @@ template <int DT> __device__ __forceinline__ float dot2_dt(uint32_t a, uint32_t 
     return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(b16x2, a), __builtin_bit_cast(b16x2, b), c, false);
 }
 
-// ---- kv8: FP8 cache rows (paged_attn_kv8.hip).  A row of D 16-bit values is D OCP E4M3 codes and one
-// scale byte s = e + 127 that stands for 2^e (s = 255: a non-finite row, every value NaN).  The scale is
+// ---- kv8: FP8 cache rows (paged_attn.hip).  A row of D 16-bit values is D OCP E4M3 codes and one scale
+// byte s = e + 127 that stands for 2^e (s = 255: a non-finite row, every value NaN).  The scale is
 // a power of two, so decode(code) * 2^e is a 16-bit value exactly and "convert at the load" leaves the
 // bits of the 16-bit launch on the dequantised cache (DESIGN, "FP8 paged KV cache").
 // The block of (page, kv head) is kAttnChunk * D code bytes, then kAttnChunk scale bytes.
@@ -173,6 +174,38 @@ __device__ __forceinline__ void kv8_put_row(float &klo, float &khi, uint32_t &vn
   klo = from_bits<DT>(kq);
   khi = from_bits<DT>(kq >> 16);
   vnew = vs == 255u ? kKv8Nan2<DT> : kv8_dq2<DT, false>(vc, kv8_scale_f32(vs));
+}
+
+// The cache writer of the window launches (k_verify_kv_write, k_prefill_kv_write, k_paged_kv_write,
+// k_kv8_kv_write): token row r, kv head h, by the threads t = 0 .. D/2 - 1 of one block -- thread t
+// rotates the pair (t, t + D/2) of k and copies one word of v.  This arithmetic defines the cache's bits.
+// `a` is the kernel's own argument block (k, v, ks, vs, cos, sin, cs, kc, vc); the caller has mapped
+// its block to (r, h), tested the row's validity and formed the address: `off` is the byte offset of
+// the row in kc / vc, or KV8: of the (page, kv head) block, with `slot` the row's place in it.
+template <int DT, int D, bool KV8, class Args>
+__device__ __forceinline__ void kv_write_row(const Args &a, long long r, int h, int t, long long off, int slot = 0) {
+  constexpr int ES = 2, H2 = D / 2;
+  const char *cb = reinterpret_cast<const char *>(a.cos) + r * a.cs * ES;
+  const char *sb = reinterpret_cast<const char *>(a.sin) + r * a.cs * ES;
+  const char *kb = reinterpret_cast<const char *>(a.k) + (r * a.ks + (long long)h * D) * ES;
+  const char *vb = reinterpret_cast<const char *>(a.v) + (r * a.vs + (long long)h * D) * ES;
+  const float k1 = load_f32<DT>(kb, t), k2 = load_f32<DT>(kb, t + H2);
+  uint32_t vnew = reinterpret_cast<const uint32_t *>(vb)[t];
+  const float c1 = load_f32<DT>(cb, t), c2 = load_f32<DT>(cb, t + H2);
+  const float s1 = load_f32<DT>(sb, t), s2 = load_f32<DT>(sb, t + H2);
+  // decode_attn_head's rope(): k*cos + cat(-k2, k1)*sin, every torch op rounded to the storage dtype
+  float lo = from_bits<DT>(bits_dt<DT>(__fadd_rn(round_dt<DT>(__fmul_rn(k1, c1)), round_dt<DT>(__fmul_rn(-k2, s1)))));
+  float hi = from_bits<DT>(bits_dt<DT>(__fadd_rn(round_dt<DT>(__fmul_rn(k2, c2)), round_dt<DT>(__fmul_rn(k1, s2)))));
+  if constexpr (KV8) {
+    kv8_put_row<DT, D>(lo, hi, vnew, t, true, reinterpret_cast<unsigned char *>(a.kc) + off,
+                       reinterpret_cast<unsigned char *>(a.vc) + off, slot);
+  } else {
+    char *kd = reinterpret_cast<char *>(a.kc) + off;
+    char *vd = reinterpret_cast<char *>(a.vc) + off;
+    store_f32<DT>(kd, t, lo);
+    store_f32<DT>(kd, t + H2, hi);
+    reinterpret_cast<uint32_t *>(vd)[t] = vnew;
+  }
 }
 
 // LDS of one head's attention.  `v` is the staged v rows, kAttnChunk x H2 words with the word
@@ -462,6 +495,38 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
     }
   }
   return p;
+}
+
+// The chunk of token row r that a per-stream kernel does not compute (its early exit, uniform over the
+// workgroup): NaN where the row is illegal (`nan`), else the neutral partial of a chunk that starts
+// above the row's position -- what a wholly masked chunk of k_decode_attn leaves (zero sums, m = -inf,
+// l = 0), so the combine is unchanged.  With one chunk only an illegal row comes here.
+template <int DT, int D>
+__device__ __forceinline__ void decode_attn_skip(const DecodeAttnArgs &a, int split, int hq, long long r, bool nan) {
+  const int t = threadIdx.x;
+  if (t < D) {
+    const float fill = nan ? __builtin_nanf("") : 0.0f;
+    if (a.nsplit == 1) {
+      char *ob = reinterpret_cast<char *>(a.out) + (r * a.os + (long long)hq * D) * 2;
+      store_f32<DT>(ob, t, fill);
+    } else {
+      const int h = hq / a.G, gq = hq - h * a.G;
+      float *pp = a.part + (((r * a.Hkv + h) * a.nsplit + split) * a.G + gq) * (D + 2);
+      pp[t] = fill;
+      if (t == 0) { pp[D] = -INFINITY; pp[D + 1] = 0.0f; }
+    }
+  }
+}
+
+// Host: f(dt, d) with the storage dtype and the head size as std::integral_constants, for the
+// launchers templated on them.  dtype F16 / BF16 and D 64 / 128 are checked by the caller.
+template <class F> void attn_dispatch(int dtype, int D, F &&f) {
+  using F16 = std::integral_constant<int, QZ_DT_F16>;
+  using BF16 = std::integral_constant<int, QZ_DT_BF16>;
+  using D64 = std::integral_constant<int, 64>;
+  using D128 = std::integral_constant<int, 128>;
+  if (dtype == QZ_DT_F16) D == 64 ? f(F16{}, D64{}) : f(F16{}, D128{});
+  else D == 64 ? f(BF16{}, D64{}) : f(BF16{}, D128{});
 }
 
 // k_decode_attn_combine (layer_ops.hip) over `rows` token rows, for the launches of other translation

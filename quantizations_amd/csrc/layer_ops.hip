@@ -254,22 +254,11 @@ template <int DT, int D>
 __global__ __launch_bounds__(256) void k_decode_attn_streams(DecodeAttnArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t s_v[kAttnChunk * (D / 2)];
   __shared__ __attribute__((aligned(16))) unsigned char s_small[AttnLds<D>::kSmallBytes];
-  const int split = blockIdx.x, hq = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
+  const int split = blockIdx.x, hq = blockIdx.y, b = blockIdx.z;
   const long long p = a.pos[b];
   const bool bad = p < 0 || p >= a.L;
   if (bad || (long long)split * kAttnChunk > p) {   // uniform over the workgroup
-    if (t < D) {
-      const float fill = bad ? __builtin_nanf("") : 0.0f;
-      if (a.nsplit == 1) {
-        char *ob = reinterpret_cast<char *>(a.out) + ((long long)b * a.os + (long long)hq * D) * 2;
-        store_f32<DT>(ob, t, fill);   // one chunk starts at 0 <= p: only a bad position comes here
-      } else {
-        const int h = hq / a.G, gq = hq - h * a.G;
-        float *pp = a.part + ((((long long)b * a.Hkv + h) * a.nsplit + split) * a.G + gq) * (D + 2);
-        pp[t] = fill;
-        if (t == 0) { pp[D] = -INFINITY; pp[D + 1] = 0.0f; }
-      }
-    }
+    decode_attn_skip<DT, D>(a, split, hq, b, bad);
     return;
   }
   const AttnLds<D> S{s_v, s_small};
@@ -294,33 +283,16 @@ struct VerifyKvArgs {
   const long long *pos;      // [B]
   int Hkv, L, T;
 };
-// grid (Hkv, B T), 64 threads: thread t < D / 2 rotates the pair (t, t + D / 2) and copies one word of v
+// grid (Hkv, B T), 64 threads: one row of kv_write_row (attn_core.h) per block
 template <int DT, int D>
 __global__ __launch_bounds__(64) void k_verify_kv_write(VerifyKvArgs a) {
-  constexpr int ES = 2, H2 = D / 2;
   const int t = threadIdx.x, h = blockIdx.x, r = blockIdx.y;
   const int b = r / a.T;
   const long long pb = a.pos[b];
-  if (t >= H2 || pb < 0 || pb >= a.L) return;
+  if (t >= D / 2 || pb < 0 || pb >= a.L) return;
   const long long p = pb + (r - b * a.T);
   if (p >= a.L) return;
-  const char *cb = reinterpret_cast<const char *>(a.cos) + (long long)r * a.cs * ES;
-  const char *sb = reinterpret_cast<const char *>(a.sin) + (long long)r * a.cs * ES;
-  const char *kb = reinterpret_cast<const char *>(a.k) + ((long long)r * a.ks + (long long)h * D) * ES;
-  const char *vb = reinterpret_cast<const char *>(a.v) + ((long long)r * a.vs + (long long)h * D) * ES;
-  const float k1 = load_f32<DT>(kb, t), k2 = load_f32<DT>(kb, t + H2);
-  const uint32_t vnew = reinterpret_cast<const uint32_t *>(vb)[t];
-  const float c1 = load_f32<DT>(cb, t), c2 = load_f32<DT>(cb, t + H2);
-  const float s1 = load_f32<DT>(sb, t), s2 = load_f32<DT>(sb, t + H2);
-  // decode_attn_head's rope(): k*cos + cat(-k2, k1)*sin, every torch op rounded to the storage dtype
-  const float lo = from_bits<DT>(bits_dt<DT>(__fadd_rn(round_dt<DT>(__fmul_rn(k1, c1)), round_dt<DT>(__fmul_rn(-k2, s1)))));
-  const float hi = from_bits<DT>(bits_dt<DT>(__fadd_rn(round_dt<DT>(__fmul_rn(k2, c2)), round_dt<DT>(__fmul_rn(k1, s2)))));
-  const long long slot = (((long long)b * a.Hkv + h) * a.L + p) * D * ES;
-  char *kd = reinterpret_cast<char *>(a.kc) + slot;
-  char *vd = reinterpret_cast<char *>(a.vc) + slot;
-  store_f32<DT>(kd, t, lo);
-  store_f32<DT>(kd, t + H2, hi);
-  reinterpret_cast<uint32_t *>(vd)[t] = vnew;
+  kv_write_row<DT, D, false>(a, r, h, t, (((long long)b * a.Hkv + h) * a.L + p) * D * 2);
 }
 
 // grid (nsplit, Hq, B T): k_decode_attn_streams with the position of token row r = blockIdx.z
@@ -328,24 +300,13 @@ template <int DT, int D>
 __global__ __launch_bounds__(256) void k_decode_attn_verify(DecodeAttnArgs a, int T) {
   __shared__ __attribute__((aligned(16))) uint32_t s_v[kAttnChunk * (D / 2)];
   __shared__ __attribute__((aligned(16))) unsigned char s_small[AttnLds<D>::kSmallBytes];
-  const int split = blockIdx.x, hq = blockIdx.y, r = blockIdx.z, t = threadIdx.x;
+  const int split = blockIdx.x, hq = blockIdx.y, r = blockIdx.z;
   const int b = r / T;
   const long long pb = a.pos[b];
   const bool bad = pb < 0 || pb >= a.L || pb + (r - b * T) >= a.L;
   const long long p = bad ? 0 : pb + (r - b * T);
   if (bad || (long long)split * kAttnChunk > p) {   // uniform over the workgroup
-    if (t < D) {
-      const float fill = bad ? __builtin_nanf("") : 0.0f;
-      if (a.nsplit == 1) {
-        char *ob = reinterpret_cast<char *>(a.out) + ((long long)r * a.os + (long long)hq * D) * 2;
-        store_f32<DT>(ob, t, fill);
-      } else {
-        const int h = hq / a.G, gq = hq - h * a.G;
-        float *pp = a.part + ((((long long)r * a.Hkv + h) * a.nsplit + split) * a.G + gq) * (D + 2);
-        pp[t] = fill;
-        if (t == 0) { pp[D] = -INFINITY; pp[D + 1] = 0.0f; }
-      }
-    }
+    decode_attn_skip<DT, D>(a, split, hq, r, bad);
     return;
   }
   const AttnLds<D> S{s_v, s_small};
@@ -733,14 +694,9 @@ __global__ __launch_bounds__(256) void k_gemv_dense(const void *__restrict__ W, 
 
 // the combine for the launches of other translation units (attn_core.h)
 void launch_decode_attn_combine(int dtype, int D, const DecodeAttnArgs &a, int rows, hipStream_t s) {
-  const dim3 g(a.Hkv, rows), b(256);
-  if (dtype == QZ_DT_F16) {
-    if (D == 64) hipLaunchKernelGGL((k_decode_attn_combine<QZ_DT_F16, 64>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_decode_attn_combine<QZ_DT_F16, 128>), g, b, 0, s, a);
-  } else {
-    if (D == 64) hipLaunchKernelGGL((k_decode_attn_combine<QZ_DT_BF16, 64>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_decode_attn_combine<QZ_DT_BF16, 128>), g, b, 0, s, a);
-  }
+  attn_dispatch(dtype, D, [&](auto dt, auto d) {
+    hipLaunchKernelGGL((k_decode_attn_combine<dt.value, d.value>), dim3(a.Hkv, rows), dim3(256), 0, s, a);
+  });
 }
 }  // namespace qz
 
@@ -860,8 +816,7 @@ extern "C" int qz_decode_attention(int dtype, int B, int Hq, int Hkv, int D, int
   a.mask = reinterpret_cast<const unsigned char *>(mask); a.mb = mask_b; a.mj = mask_j;
   a.arrive = arrive;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == QZ_DT_F16) D == 64 ? launch_decode_attn<QZ_DT_F16, 64>(a, B, s) : launch_decode_attn<QZ_DT_F16, 128>(a, B, s);
-  else D == 64 ? launch_decode_attn<QZ_DT_BF16, 64>(a, B, s) : launch_decode_attn<QZ_DT_BF16, 128>(a, B, s);
+  attn_dispatch(dtype, D, [&](auto dt, auto d) { launch_decode_attn<dt.value, d.value>(a, B, s); });
   return (int)hipGetLastError();
 }
 
@@ -875,8 +830,7 @@ extern "C" int qz_decode_attention_streams(int dtype, int B, int Hq, int Hkv, in
                                   v_cache, true, pos, out, out_row, work, scale, a);
   if (rc <= 0) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == QZ_DT_F16) D == 64 ? launch_decode_attn_streams<QZ_DT_F16, 64>(a, B, s) : launch_decode_attn_streams<QZ_DT_F16, 128>(a, B, s);
-  else D == 64 ? launch_decode_attn_streams<QZ_DT_BF16, 64>(a, B, s) : launch_decode_attn_streams<QZ_DT_BF16, 128>(a, B, s);
+  attn_dispatch(dtype, D, [&](auto dt, auto d) { launch_decode_attn_streams<dt.value, d.value>(a, B, s); });
   return (int)hipGetLastError();
 }
 
@@ -893,8 +847,7 @@ extern "C" int qz_decode_attention_verify(int dtype, int B, int T, int Hq, int H
                                   v_cache, true, pos, out, out_row, work, scale, a);
   if (rc <= 0) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == QZ_DT_F16) D == 64 ? launch_decode_attn_verify<QZ_DT_F16, 64>(a, B, T, s) : launch_decode_attn_verify<QZ_DT_F16, 128>(a, B, T, s);
-  else D == 64 ? launch_decode_attn_verify<QZ_DT_BF16, 64>(a, B, T, s) : launch_decode_attn_verify<QZ_DT_BF16, 128>(a, B, T, s);
+  attn_dispatch(dtype, D, [&](auto dt, auto d) { launch_decode_attn_verify<dt.value, d.value>(a, B, T, s); });
   return (int)hipGetLastError();
 }
 

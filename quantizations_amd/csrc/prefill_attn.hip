@@ -2,9 +2,9 @@
 // against a static KV cache, O(visible keys), on the gfx950 matrix cores.
 //
 // Token row (b, i), i < len[b], sits at position pos[b] + i of cache row b.  Two launches:
-//   1. k_prefill_kv_write: k_verify_kv_write (layer_ops.hip) with a length operand -- the same
-//      rotate-and-store arithmetic (decode_attn_head's rope(), every torch op rounded to the storage
-//      dtype), so the cache holds the bits a decode step at that position stores.
+//   1. k_prefill_kv_write: k_verify_kv_write (layer_ops.hip) with a length operand -- both call the one
+//      rotate-and-store writer, kv_write_row (attn_core.h: decode_attn_head's rope(), every torch op
+//      rounded to the storage dtype), so the cache holds the bits a decode step at that position stores.
 //   2. k_prefill_attn: one workgroup of 4 waves per (query tile of kPfTQ rows, query head, stream).
 //      It reads the caches only (the window's own keys included, written by launch 1).
 //
@@ -38,33 +38,15 @@
 
 namespace qz {
 
-// grid (T, Hkv, B), 64 threads: thread t < D / 2 rotates the pair (t, t + D / 2) and copies one word of v
+// grid (T, Hkv, B), 64 threads: one row of kv_write_row (attn_core.h) per block
 template <int DT, int D>
 __global__ __launch_bounds__(64) void k_prefill_kv_write(PrefillArgs a) {
-  constexpr int ES = 2, H2 = D / 2;
   const int t = threadIdx.x, i = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const long long pb = a.pos[b];
-  if (t >= H2 || i >= a.len[b] || pb < 0 || pb >= a.L) return;
+  if (t >= D / 2 || i >= a.len[b] || pb < 0 || pb >= a.L) return;
   const long long p = pb + i;
   if (p >= a.L) return;
-  const long long r = (long long)b * a.T + i;
-  const char *cb = reinterpret_cast<const char *>(a.cos) + r * a.cs * ES;
-  const char *sb = reinterpret_cast<const char *>(a.sin) + r * a.cs * ES;
-  const char *kb = reinterpret_cast<const char *>(a.k) + (r * a.ks + (long long)h * D) * ES;
-  const char *vb = reinterpret_cast<const char *>(a.v) + (r * a.vs + (long long)h * D) * ES;
-  const float k1 = load_f32<DT>(kb, t), k2 = load_f32<DT>(kb, t + H2);
-  const uint32_t vnew = reinterpret_cast<const uint32_t *>(vb)[t];
-  const float c1 = load_f32<DT>(cb, t), c2 = load_f32<DT>(cb, t + H2);
-  const float s1 = load_f32<DT>(sb, t), s2 = load_f32<DT>(sb, t + H2);
-  // decode_attn_head's rope(): k*cos + cat(-k2, k1)*sin, every torch op rounded to the storage dtype
-  const float lo = from_bits<DT>(bits_dt<DT>(__fadd_rn(round_dt<DT>(__fmul_rn(k1, c1)), round_dt<DT>(__fmul_rn(-k2, s1)))));
-  const float hi = from_bits<DT>(bits_dt<DT>(__fadd_rn(round_dt<DT>(__fmul_rn(k2, c2)), round_dt<DT>(__fmul_rn(k1, s2)))));
-  const long long slot = (((long long)b * a.Hkv + h) * a.L + p) * D * ES;
-  char *kd = reinterpret_cast<char *>(a.kc) + slot;
-  char *vd = reinterpret_cast<char *>(a.vc) + slot;
-  store_f32<DT>(kd, t, lo);
-  store_f32<DT>(kd, t + H2, hi);
-  reinterpret_cast<uint32_t *>(vd)[t] = vnew;
+  kv_write_row<DT, D, false>(a, (long long)b * a.T + i, h, t, (((long long)b * a.Hkv + h) * a.L + p) * D * 2);
 }
 
 // grid (ceil(T / kPfTQ), Hq, B), 256 threads
@@ -109,7 +91,6 @@ extern "C" int qz_prefill_attention(int dtype, int B, int T, int Hq, int Hkv, in
   a.out = out; a.os = out_row;
   a.T = T; a.Hkv = Hkv; a.G = Hq / Hkv; a.L = L; a.scale = scale;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == QZ_DT_F16) D == 64 ? launch_prefill_attn<QZ_DT_F16, 64>(a, B, s) : launch_prefill_attn<QZ_DT_F16, 128>(a, B, s);
-  else D == 64 ? launch_prefill_attn<QZ_DT_BF16, 64>(a, B, s) : launch_prefill_attn<QZ_DT_BF16, 128>(a, B, s);
+  attn_dispatch(dtype, D, [&](auto dt, auto d) { launch_prefill_attn<dt.value, d.value>(a, B, s); });
   return (int)hipGetLastError();
 }

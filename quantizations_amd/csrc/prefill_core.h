@@ -63,7 +63,7 @@ template <int DT> __device__ __forceinline__ pf_f4 pf_mfma(const u32x4 a, const 
 // [0, P) is never turned into an address: its keys are staged as zeros and every row that can see
 // one of them (position >= 128 (jt >> 1)) is NaN.  A row below it masks those keys to weight 0 as it
 // does the real keys it cannot see, and keeps the contiguous kernel's bits.
-// KV8 (with PAGED, paged_attn_kv8.hip): the pools hold kv8 blocks (attn_core.h).  load_tile reads 16
+// KV8 (with PAGED, paged_attn.hip): the pools hold kv8 blocks (attn_core.h).  load_tile reads 16
 // codes per 16-B load and the key's scale byte -- half the loads and half the registers in flight
 // during the MFMAs; store_tile converts them in registers and writes the same LDS image, so the
 // MFMA loop sees the 16-bit operands of the paged kernel on the dequantised cache.

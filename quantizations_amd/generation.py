@@ -481,7 +481,7 @@ class PagedKVCache:
     a 4-D mask given, the decoder's forward asks nothing of it, and the fused attention reads
     .layers[i] only; anything that tried to use it as a transformers cache ends in update().
     kv_dtype="fp8": the pools are kv8 byte pools, uint8 [P, Hkv, 128 (D + 1)] -- per (page, kv head) 128 D
-    E4M3 codes, then 128 power-of-two scale bytes (csrc/paged_attn_kv8.hip) -- which the *_paged_kv8
+    E4M3 codes, then 128 power-of-two scale bytes (csrc/paged_attn.hip) -- which the *_paged_kv8
     launches read and write; a zero-filled page reads as zeros there too.  A page is still pool[page]."""
 
     def __init__(self, config, num_pages: int, dtype, device, kv_dtype: Optional[str] = None):

@@ -331,13 +331,13 @@ def _fused_attention_forward(mod: nn.Module, orig):
             raise ValueError("_qz_paged: the paged launches need a PagedKVCache layer of this module's head_dim")
         table, = paged
         keys, values = layer.keys, layer.values
-        sfx = "_kv8" if kv8 else ""
-        prefill_paged, prefill_ok = (getattr(layer_ops, "prefill_attention_paged" + sfx),
-                                     getattr(layer_ops, "prefill_attention_paged" + sfx + "_supported"))
-        verify_paged, verify_ok = (getattr(layer_ops, "decode_attention_verify_paged" + sfx),
-                                   getattr(layer_ops, "decode_attention_verify_paged" + sfx + "_supported"))
-        decode_paged, decode_ok = (getattr(layer_ops, "decode_attention_paged" + sfx),
-                                   getattr(layer_ops, "decode_attention_paged" + sfx + "_supported"))
+        (prefill_paged, prefill_ok, verify_paged, verify_ok, decode_paged, decode_ok) = (
+            (layer_ops.prefill_attention_paged_kv8, layer_ops.prefill_attention_paged_kv8_supported,
+             layer_ops.decode_attention_verify_paged_kv8, layer_ops.decode_attention_verify_paged_kv8_supported,
+             layer_ops.decode_attention_paged_kv8, layer_ops.decode_attention_paged_kv8_supported) if kv8 else
+            (layer_ops.prefill_attention_paged, layer_ops.prefill_attention_paged_supported,
+             layer_ops.decode_attention_verify_paged, layer_ops.decode_attention_verify_paged_supported,
+             layer_ops.decode_attention_paged, layer_ops.decode_attention_paged_supported))
         cos, sin = position_embeddings
         nq = keys.shape[1] * (mod.config.num_attention_heads // mod.config.num_key_value_heads)
         if prefill is not None:

@@ -302,23 +302,12 @@ def decode_attention_verify(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, c
         raise ValueError("decode_attention_verify: unsupported shapes/dtypes/layout")
     B, Hkv, L, D = key_cache.shape
     T, G = q.shape[1], num_heads // Hkv
-    if q.shape[2] != num_heads * D:
-        raise ValueError("decode_attention_verify: q width differs from num_heads * head_dim")
-    if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
-        raise ValueError("decode_attention_verify: sin must match cos")
-    if k.shape[:2] != q.shape[:2] or v.shape[:2] != q.shape[:2]:
-        raise ValueError("decode_attention_verify: k/v must hold q's [B, T] rows")
-    R = B * T
-    q2, k2, v2 = (t.reshape(R, -1) for t in (q, k, v))
-    k2 = k2 if k2.stride(-1) == 1 else k2.contiguous()
-    q2 = q2 if q2.stride(-1) == 1 else q2.contiguous()
-    if v2.stride(-1) != 1 or v2.stride(0) % 2 or v2.data_ptr() % 4:
-        v2 = v2.contiguous()
-    if k2.shape[1] != Hkv * D or v2.shape[1] != Hkv * D:
-        raise ValueError("decode_attention_verify: k/v width differs from the cache's heads")
+    _check_window("decode_attention_verify", q, k, v, cos, sin, num_heads, D)
+    q2, k2, v2 = _verify_rows("decode_attention_verify", q, k, v, Hkv * D, "cache's")
     out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
     nsplit = -(-L // ATTN_CHUNK)
-    work = torch.empty(R * Hkv * nsplit * G * (D + 2), dtype=torch.float32, device=q.device) if nsplit > 1 else None
+    work = (torch.empty(B * T * Hkv * nsplit * G * (D + 2), dtype=torch.float32, device=q.device) if nsplit > 1
+            else None)
     _lib.check(_lib.lib.qz_decode_attention_verify(
         _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, L, q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0),
         v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cos.stride(1), key_cache.data_ptr(),
@@ -377,36 +366,10 @@ def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: to
         raise ValueError("prefill_attention: unsupported shapes/dtypes/layout")
     B, Hkv, L, D = key_cache.shape
     T = q.shape[1]
-    if q.shape[2] != num_heads * D:
-        raise ValueError("prefill_attention: q width differs from num_heads * head_dim")
-    if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
-        raise ValueError("prefill_attention: sin must match cos")
-    if k.shape[:2] != q.shape[:2] or v.shape[:2] != q.shape[:2]:
-        raise ValueError("prefill_attention: k/v must hold q's [B, T] rows")
+    _check_window("prefill_attention", q, k, v, cos, sin, num_heads, D)
     if k.shape[2] != Hkv * D or v.shape[2] != Hkv * D:
         raise ValueError("prefill_attention: k/v width differs from the cache's heads")
-    R = B * T
-
-    def rows(t, align, mult):
-        # [B, T, W] as R rows at one stride (a multiple of `mult` elements) from an `align`-byte base
-        W = t.shape[2]
-        if t.shape[0] != B:
-            t = t.expand(B, -1, -1)
-        t = t.reshape(R, W)   # a view where the rows lie at one stride, a copy otherwise
-        if R == 1 and t.stride(-1) == 1 and t.data_ptr() % align == 0:
-            return t, W
-        if t.stride(-1) != 1 or t.stride(0) < W or t.stride(0) % mult or t.data_ptr() % align:
-            t = t.contiguous()
-        return t, t.stride(0)
-
-    q2, qs = rows(q, 16, 8)
-    k2, ks = rows(k, 2, 1)
-    v2, vs = rows(v, 4, 2)
-    c2, cs = rows(cos, 16, 8)
-    s2, ss = rows(sin, 16, 8)
-    if ss != cs:
-        s2, c2 = s2.contiguous(), c2.contiguous()
-        cs = D
+    q2, qs, k2, ks, v2, vs, c2, s2, cs = _prefill_rows(q, k, v, cos, sin, B, T, D)
     out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
     _lib.check(_lib.lib.qz_prefill_attention(
         _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, L, q2.data_ptr(), qs, k2.data_ptr(), ks, v2.data_ptr(), vs,
@@ -421,10 +384,16 @@ KV_PAGE = 128  # positions per page of the paged cache (qz_kv_page_size(): the d
 KV8_ROW_EXTRA = 1  # bytes a kv8 cache row carries beyond its D codes: the scale byte
 
 
-def _kv8_geometry(k_pool, v_pool):
-    """(P, Hkv, D) of a pair of kv8 pools, uint8 [P, Hkv, 128 (D + 1)]; None for anything else."""
-    if not (isinstance(k_pool, torch.Tensor) and isinstance(v_pool, torch.Tensor) and k_pool.dim() == 3
-            and v_pool.shape == k_pool.shape and k_pool.dtype == torch.uint8):
+def _pool_geometry(k_pool, v_pool, kv8: bool):
+    """(P, Hkv, D) of a pair of page pools -- [P, Hkv, 128, D], or kv8: uint8 [P, Hkv, 128 (D + 1)];
+    None for anything else."""
+    if not (isinstance(k_pool, torch.Tensor) and isinstance(v_pool, torch.Tensor)
+            and k_pool.dim() == (3 if kv8 else 4) and v_pool.shape == k_pool.shape):
+        return None
+    if not kv8:
+        P, Hkv, page, D = k_pool.shape
+        return (P, Hkv, D) if page == KV_PAGE else None
+    if k_pool.dtype != torch.uint8:
         return None
     P, Hkv, W = k_pool.shape
     D = W // KV_PAGE - KV8_ROW_EXTRA
@@ -439,16 +408,10 @@ def _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads: int
     if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype in (torch.float16, torch.bfloat16)
             and q.dim() == 3 and q.shape[1] >= min_t) or _needs_grad(q):
         return False
-    if kv8:
-        geometry = _kv8_geometry(k_pool, v_pool)
-        if geometry is None:
-            return False
-        P, Hkv, D = geometry
-    else:
-        if not (isinstance(k_pool, torch.Tensor) and isinstance(v_pool, torch.Tensor) and k_pool.dim() == 4
-                and v_pool.shape == k_pool.shape and k_pool.shape[2] == KV_PAGE):
-            return False
-        P, Hkv, _, D = k_pool.shape
+    geometry = _pool_geometry(k_pool, v_pool, kv8)
+    if geometry is None:
+        return False
+    P, Hkv, D = geometry
     B, T = q.shape[0], q.shape[1]
     if (D not in (64, 128) or Hkv == 0 or P == 0 or num_heads % Hkv or num_heads // Hkv > 8 or B > 65535
             or num_heads > 65535):
@@ -468,14 +431,94 @@ def _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads: int
             and pos.device == q.device and pos.is_contiguous())
 
 
+def _decode_paged_supported(q, cos, k_pool, v_pool, table, pos, num_heads: int, kv8: bool) -> bool:
+    return (isinstance(q, torch.Tensor) and q.dim() == 3 and q.shape[1] == 1
+            and _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 1, lambda B: (1, B), kv8))
+
+
+def _verify_paged_supported(q, cos, k_pool, v_pool, table, pos, num_heads: int, kv8: bool) -> bool:
+    if not _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 2, lambda B: (B,), kv8):
+        return False
+    B, T = q.shape[0], q.shape[1]
+    return B * T <= 65535 and (B == 1 or cos.stride(0) == T * cos.stride(1))
+
+
+def _prefill_paged_supported(q, cos, k_pool, v_pool, table, pos, length, num_heads: int, kv8: bool) -> bool:
+    if not _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 1, lambda B: (1, B), kv8):
+        return False
+    return (isinstance(length, torch.Tensor) and length.dtype == torch.int64 and length.dim() == 1
+            and length.shape[0] == q.shape[0] and length.device == q.device and length.is_contiguous())
+
+
+def _decode_paged(q, k, v, cos, sin, k_pool, v_pool, table, pos, num_heads: int, scale: float, kv8: bool):
+    """decode_attention_paged and decode_attention_paged_kv8: one launch, two pool formats."""
+    name = "decode_attention_paged_kv8" if kv8 else "decode_attention_paged"
+    if not _decode_paged_supported(q, cos, k_pool, v_pool, table, pos, num_heads, kv8):
+        raise ValueError(f"{name}: unsupported shapes/dtypes/layout")
+    P, Hkv, D = _pool_geometry(k_pool, v_pool, kv8)
+    B, NP = table.shape
+    # _attention_launch_operands reads only the shape of its cache operand: [B, Hkv, L, D]
+    shape = q.as_strided((B, Hkv, NP * KV_PAGE, D), (0, 0, 0, 0))
+    q2, k2, v2, out, work, cs_row = _attention_launch_operands(name, q, k, v, cos, sin, shape, num_heads)
+    launch = _lib.lib.qz_decode_attention_paged_kv8 if kv8 else _lib.lib.qz_decode_attention_paged
+    _lib.check(launch(
+        _lib.dtype_code(q.dtype), B, num_heads, Hkv, D, NP, P, q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0),
+        v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cs_row, k_pool.data_ptr(), v_pool.data_ptr(),
+        table.data_ptr(), table.stride(0), pos.data_ptr(), out.data_ptr(), num_heads * D,
+        work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)), "qz_" + name)
+    return out
+
+
+def _verify_paged(q, k, v, cos, sin, k_pool, v_pool, table, pos, num_heads: int, scale: float, kv8: bool):
+    """decode_attention_verify_paged and decode_attention_verify_paged_kv8: one launch, two pool formats."""
+    name = "decode_attention_verify_paged_kv8" if kv8 else "decode_attention_verify_paged"
+    if not _verify_paged_supported(q, cos, k_pool, v_pool, table, pos, num_heads, kv8):
+        raise ValueError(f"{name}: unsupported shapes/dtypes/layout")
+    P, Hkv, D = _pool_geometry(k_pool, v_pool, kv8)
+    B, NP = table.shape
+    T, G = q.shape[1], num_heads // Hkv
+    _check_window(name, q, k, v, cos, sin, num_heads, D)
+    q2, k2, v2 = _verify_rows(name, q, k, v, Hkv * D, "pools'")
+    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
+    work = torch.empty(B * T * Hkv * NP * G * (D + 2), dtype=torch.float32, device=q.device) if NP > 1 else None
+    launch = _lib.lib.qz_decode_attention_verify_paged_kv8 if kv8 else _lib.lib.qz_decode_attention_verify_paged
+    _lib.check(launch(
+        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, NP, P, q2.data_ptr(), q2.stride(0), k2.data_ptr(),
+        k2.stride(0), v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cos.stride(1), k_pool.data_ptr(),
+        v_pool.data_ptr(), table.data_ptr(), table.stride(0), pos.data_ptr(), out.data_ptr(), num_heads * D,
+        work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)), "qz_" + name)
+    return out
+
+
+def _prefill_paged(q, k, v, cos, sin, k_pool, v_pool, table, pos, length, num_heads: int, scale: float, kv8: bool):
+    """prefill_attention_paged and prefill_attention_paged_kv8: one launch, two pool formats."""
+    name = "prefill_attention_paged_kv8" if kv8 else "prefill_attention_paged"
+    if not _prefill_paged_supported(q, cos, k_pool, v_pool, table, pos, length, num_heads, kv8):
+        raise ValueError(f"{name}: unsupported shapes/dtypes/layout")
+    P, Hkv, D = _pool_geometry(k_pool, v_pool, kv8)
+    B, NP = table.shape
+    T = q.shape[1]
+    _check_window(name, q, k, v, cos, sin, num_heads, D)
+    if k.shape[2] != Hkv * D or v.shape[2] != Hkv * D:
+        raise ValueError(f"{name}: k/v width differs from the pools' heads")
+    q2, qs, k2, ks, v2, vs, c2, s2, cs = _prefill_rows(q, k, v, cos, sin, B, T, D)
+    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
+    launch = _lib.lib.qz_prefill_attention_paged_kv8 if kv8 else _lib.lib.qz_prefill_attention_paged
+    _lib.check(launch(
+        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, NP, P, q2.data_ptr(), qs, k2.data_ptr(), ks, v2.data_ptr(),
+        vs, c2.data_ptr(), s2.data_ptr(), cs, k_pool.data_ptr(), v_pool.data_ptr(), table.data_ptr(), table.stride(0),
+        pos.data_ptr(), length.data_ptr(), out.data_ptr(), num_heads * D, float(scale), _lib.stream_of(q)),
+        "qz_" + name)
+    return out
+
+
 def decode_attention_paged_supported(q: torch.Tensor, cos: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
                                      table, pos, num_heads: int) -> bool:
     """What qz_decode_attention_paged takes: one new token per stream (q [B, 1, *]), 16-bit
     activations, pools [P, Hkv, 128, D] with D in {64, 128} and Hq/Hkv <= 8, a table int32 [B, NP] with
     unit inner stride, cos/sin [B or 1, 1, D] and pos int64 [B], all on q's device.  Metadata only:
     nothing is launched or allocated."""
-    return (isinstance(q, torch.Tensor) and q.dim() == 3 and q.shape[1] == 1
-            and _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 1, lambda B: (1, B)))
+    return _decode_paged_supported(q, cos, k_pool, v_pool, table, pos, num_heads, False)
 
 
 def decode_attention_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
@@ -487,20 +530,7 @@ def decode_attention_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, co
     decode_attention_streams on the cache the table gathers.  A table entry outside [0, P) that the
     stream needs makes its row NaN and is never dereferenced; entries above pos[b] >> 7 may hold
     anything.  Returns [B, 1, Hq*D]."""
-    if not decode_attention_paged_supported(q, cos, k_pool, v_pool, table, pos, num_heads):
-        raise ValueError("decode_attention_paged: unsupported shapes/dtypes/layout")
-    P, Hkv, _, D = k_pool.shape
-    B, NP = table.shape
-    # _attention_launch_operands reads only the shape of its cache operand: [B, Hkv, L, D]
-    shape = k_pool.as_strided((B, Hkv, NP * KV_PAGE, D), (0, 0, 0, 0))
-    q2, k2, v2, out, work, cs_row = _attention_launch_operands("decode_attention_paged", q, k, v, cos, sin, shape,
-                                                               num_heads)
-    _lib.check(_lib.lib.qz_decode_attention_paged(
-        _lib.dtype_code(q.dtype), B, num_heads, Hkv, D, NP, P, q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0),
-        v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cs_row, k_pool.data_ptr(), v_pool.data_ptr(),
-        table.data_ptr(), table.stride(0), pos.data_ptr(), out.data_ptr(), num_heads * D,
-        work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)), "qz_decode_attention_paged")
-    return out
+    return _decode_paged(q, k, v, cos, sin, k_pool, v_pool, table, pos, num_heads, scale, False)
 
 
 def decode_attention_verify_paged_supported(q: torch.Tensor, cos: torch.Tensor, k_pool: torch.Tensor,
@@ -508,10 +538,7 @@ def decode_attention_verify_paged_supported(q: torch.Tensor, cos: torch.Tensor, 
     """What qz_decode_attention_verify_paged takes: T >= 2 new tokens per stream (q [B, T, *]),
     decode_attention_paged_supported's pools, table and pos, and cos/sin [B, T, D] whose B T rows lie
     at one stride.  Metadata only: nothing is launched or allocated."""
-    if not _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 2, lambda B: (B,)):
-        return False
-    B, T = q.shape[0], q.shape[1]
-    return B * T <= 65535 and (B == 1 or cos.stride(0) == T * cos.stride(1))
+    return _verify_paged_supported(q, cos, k_pool, v_pool, table, pos, num_heads, False)
 
 
 def decode_attention_verify_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor,
@@ -522,34 +549,7 @@ def decode_attention_verify_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Ten
     0..pos[b] + i.  Bits are decode_attention_verify's on the gathered cache; a row that needs an
     entry outside [0, P) is NaN and a row whose write entry is invalid writes nothing.  Returns
     [B, T, Hq*D]."""
-    if not decode_attention_verify_paged_supported(q, cos, k_pool, v_pool, table, pos, num_heads):
-        raise ValueError("decode_attention_verify_paged: unsupported shapes/dtypes/layout")
-    P, Hkv, _, D = k_pool.shape
-    B, NP = table.shape
-    T, G = q.shape[1], num_heads // Hkv
-    if q.shape[2] != num_heads * D:
-        raise ValueError("decode_attention_verify_paged: q width differs from num_heads * head_dim")
-    if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
-        raise ValueError("decode_attention_verify_paged: sin must match cos")
-    if k.shape[:2] != q.shape[:2] or v.shape[:2] != q.shape[:2]:
-        raise ValueError("decode_attention_verify_paged: k/v must hold q's [B, T] rows")
-    R = B * T
-    q2, k2, v2 = (t.reshape(R, -1) for t in (q, k, v))
-    k2 = k2 if k2.stride(-1) == 1 else k2.contiguous()
-    q2 = q2 if q2.stride(-1) == 1 else q2.contiguous()
-    if v2.stride(-1) != 1 or v2.stride(0) % 2 or v2.data_ptr() % 4:
-        v2 = v2.contiguous()
-    if k2.shape[1] != Hkv * D or v2.shape[1] != Hkv * D:
-        raise ValueError("decode_attention_verify_paged: k/v width differs from the pools' heads")
-    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
-    work = torch.empty(R * Hkv * NP * G * (D + 2), dtype=torch.float32, device=q.device) if NP > 1 else None
-    _lib.check(_lib.lib.qz_decode_attention_verify_paged(
-        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, NP, P, q2.data_ptr(), q2.stride(0), k2.data_ptr(),
-        k2.stride(0), v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cos.stride(1), k_pool.data_ptr(),
-        v_pool.data_ptr(), table.data_ptr(), table.stride(0), pos.data_ptr(), out.data_ptr(), num_heads * D,
-        work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)),
-        "qz_decode_attention_verify_paged")
-    return out
+    return _verify_paged(q, k, v, cos, sin, k_pool, v_pool, table, pos, num_heads, scale, False)
 
 
 def prefill_attention_paged_supported(q: torch.Tensor, cos: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
@@ -557,10 +557,7 @@ def prefill_attention_paged_supported(q: torch.Tensor, cos: torch.Tensor, k_pool
     """What qz_prefill_attention_paged takes: T >= 1 new tokens per stream (q [B, T, *]),
     decode_attention_paged_supported's pools, table and pos, cos/sin [B or 1, T, D] with unit inner
     stride and an int64 length [B].  Metadata only: nothing is launched or allocated."""
-    if not _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 1, lambda B: (1, B)):
-        return False
-    return (isinstance(length, torch.Tensor) and length.dtype == torch.int64 and length.dim() == 1
-            and length.shape[0] == q.shape[0] and length.device == q.device and length.is_contiguous())
+    return _prefill_paged_supported(q, cos, k_pool, v_pool, table, pos, length, num_heads, False)
 
 
 def prefill_attention_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
@@ -572,34 +569,7 @@ def prefill_attention_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, c
     on the gathered cache, so a window split into several calls equals the whole window.  A row that
     needs an entry outside [0, P) is NaN; a row whose write entry is invalid writes nothing.  Returns
     [B, T, Hq*D]."""
-    if not prefill_attention_paged_supported(q, cos, k_pool, v_pool, table, pos, length, num_heads):
-        raise ValueError("prefill_attention_paged: unsupported shapes/dtypes/layout")
-    P, Hkv, _, D = k_pool.shape
-    B, NP = table.shape
-    T = q.shape[1]
-    if q.shape[2] != num_heads * D:
-        raise ValueError("prefill_attention_paged: q width differs from num_heads * head_dim")
-    if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
-        raise ValueError("prefill_attention_paged: sin must match cos")
-    if k.shape[:2] != q.shape[:2] or v.shape[:2] != q.shape[:2]:
-        raise ValueError("prefill_attention_paged: k/v must hold q's [B, T] rows")
-    if k.shape[2] != Hkv * D or v.shape[2] != Hkv * D:
-        raise ValueError("prefill_attention_paged: k/v width differs from the pools' heads")
-    q2, qs = _token_rows(q, B, T, 16, 8)
-    k2, ks = _token_rows(k, B, T, 2, 1)
-    v2, vs = _token_rows(v, B, T, 4, 2)
-    c2, cs = _token_rows(cos, B, T, 16, 8)
-    s2, ss = _token_rows(sin, B, T, 16, 8)
-    if ss != cs:
-        s2, c2 = s2.contiguous(), c2.contiguous()
-        cs = D
-    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
-    _lib.check(_lib.lib.qz_prefill_attention_paged(
-        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, NP, P, q2.data_ptr(), qs, k2.data_ptr(), ks, v2.data_ptr(),
-        vs, c2.data_ptr(), s2.data_ptr(), cs, k_pool.data_ptr(), v_pool.data_ptr(), table.data_ptr(), table.stride(0),
-        pos.data_ptr(), length.data_ptr(), out.data_ptr(), num_heads * D, float(scale), _lib.stream_of(q)),
-        "qz_prefill_attention_paged")
-    return out
+    return _prefill_paged(q, k, v, cos, sin, k_pool, v_pool, table, pos, length, num_heads, scale, False)
 
 
 def decode_attention_paged_kv8_supported(q: torch.Tensor, cos: torch.Tensor, k_pool: torch.Tensor,
@@ -607,8 +577,7 @@ def decode_attention_paged_kv8_supported(q: torch.Tensor, cos: torch.Tensor, k_p
     """What qz_decode_attention_paged_kv8 takes: decode_attention_paged_supported's operands with kv8
     pools, uint8 [P, Hkv, 128 (D + 1)] with D in {64, 128}, contiguous and 16-B aligned, in place of the
     16-bit ones.  Metadata only."""
-    return (isinstance(q, torch.Tensor) and q.dim() == 3 and q.shape[1] == 1
-            and _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 1, lambda B: (1, B), True))
+    return _decode_paged_supported(q, cos, k_pool, v_pool, table, pos, num_heads, True)
 
 
 def decode_attention_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor,
@@ -619,31 +588,14 @@ def decode_attention_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
     and scored as they will read back, so the output carries the bits of decode_attention_paged with
     identity cos/sin on the dequantised pools, the rotated q and the dequantised new rows.  Validity
     rules are decode_attention_paged's.  Returns [B, 1, Hq*D]."""
-    if not decode_attention_paged_kv8_supported(q, cos, k_pool, v_pool, table, pos, num_heads):
-        raise ValueError("decode_attention_paged_kv8: unsupported shapes/dtypes/layout")
-    P, Hkv, D = _kv8_geometry(k_pool, v_pool)
-    B, NP = table.shape
-    # _attention_launch_operands reads only the shape of its cache operand: [B, Hkv, L, D]
-    shape = q.as_strided((B, Hkv, NP * KV_PAGE, D), (0, 0, 0, 0))
-    q2, k2, v2, out, work, cs_row = _attention_launch_operands("decode_attention_paged_kv8", q, k, v, cos, sin, shape,
-                                                               num_heads)
-    _lib.check(_lib.lib.qz_decode_attention_paged_kv8(
-        _lib.dtype_code(q.dtype), B, num_heads, Hkv, D, NP, P, q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0),
-        v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cs_row, k_pool.data_ptr(), v_pool.data_ptr(),
-        table.data_ptr(), table.stride(0), pos.data_ptr(), out.data_ptr(), num_heads * D,
-        work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)),
-        "qz_decode_attention_paged_kv8")
-    return out
+    return _decode_paged(q, k, v, cos, sin, k_pool, v_pool, table, pos, num_heads, scale, True)
 
 
 def decode_attention_verify_paged_kv8_supported(q: torch.Tensor, cos: torch.Tensor, k_pool: torch.Tensor,
                                                 v_pool: torch.Tensor, table, pos, num_heads: int) -> bool:
     """What qz_decode_attention_verify_paged_kv8 takes: decode_attention_verify_paged_supported's
     operands with kv8 pools.  Metadata only."""
-    if not _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 2, lambda B: (B,), True):
-        return False
-    B, T = q.shape[0], q.shape[1]
-    return B * T <= 65535 and (B == 1 or cos.stride(0) == T * cos.stride(1))
+    return _verify_paged_supported(q, cos, k_pool, v_pool, table, pos, num_heads, True)
 
 
 def decode_attention_verify_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor,
@@ -654,44 +606,14 @@ def decode_attention_verify_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch
     rows of every stream are rotated, quantised and stored first, then every token reads its keys,
     slot pos[b] + i included, from the pools.  One call equals T successive decode_attention_paged_kv8
     calls in outputs and pool bytes.  Returns [B, T, Hq*D]."""
-    if not decode_attention_verify_paged_kv8_supported(q, cos, k_pool, v_pool, table, pos, num_heads):
-        raise ValueError("decode_attention_verify_paged_kv8: unsupported shapes/dtypes/layout")
-    P, Hkv, D = _kv8_geometry(k_pool, v_pool)
-    B, NP = table.shape
-    T, G = q.shape[1], num_heads // Hkv
-    if q.shape[2] != num_heads * D:
-        raise ValueError("decode_attention_verify_paged_kv8: q width differs from num_heads * head_dim")
-    if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
-        raise ValueError("decode_attention_verify_paged_kv8: sin must match cos")
-    if k.shape[:2] != q.shape[:2] or v.shape[:2] != q.shape[:2]:
-        raise ValueError("decode_attention_verify_paged_kv8: k/v must hold q's [B, T] rows")
-    R = B * T
-    q2, k2, v2 = (t.reshape(R, -1) for t in (q, k, v))
-    k2 = k2 if k2.stride(-1) == 1 else k2.contiguous()
-    q2 = q2 if q2.stride(-1) == 1 else q2.contiguous()
-    if v2.stride(-1) != 1 or v2.stride(0) % 2 or v2.data_ptr() % 4:
-        v2 = v2.contiguous()
-    if k2.shape[1] != Hkv * D or v2.shape[1] != Hkv * D:
-        raise ValueError("decode_attention_verify_paged_kv8: k/v width differs from the pools' heads")
-    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
-    work = torch.empty(R * Hkv * NP * G * (D + 2), dtype=torch.float32, device=q.device) if NP > 1 else None
-    _lib.check(_lib.lib.qz_decode_attention_verify_paged_kv8(
-        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, NP, P, q2.data_ptr(), q2.stride(0), k2.data_ptr(),
-        k2.stride(0), v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cos.stride(1), k_pool.data_ptr(),
-        v_pool.data_ptr(), table.data_ptr(), table.stride(0), pos.data_ptr(), out.data_ptr(), num_heads * D,
-        work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)),
-        "qz_decode_attention_verify_paged_kv8")
-    return out
+    return _verify_paged(q, k, v, cos, sin, k_pool, v_pool, table, pos, num_heads, scale, True)
 
 
 def prefill_attention_paged_kv8_supported(q: torch.Tensor, cos: torch.Tensor, k_pool: torch.Tensor,
                                           v_pool: torch.Tensor, table, pos, length, num_heads: int) -> bool:
     """What qz_prefill_attention_paged_kv8 takes: prefill_attention_paged_supported's operands with kv8
     pools.  Metadata only."""
-    if not _paged_operands_supported(q, cos, k_pool, v_pool, table, pos, num_heads, 1, lambda B: (1, B), True):
-        return False
-    return (isinstance(length, torch.Tensor) and length.dtype == torch.int64 and length.dim() == 1
-            and length.shape[0] == q.shape[0] and length.device == q.device and length.is_contiguous())
+    return _prefill_paged_supported(q, cos, k_pool, v_pool, table, pos, length, num_heads, True)
 
 
 def prefill_attention_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor,
@@ -701,19 +623,36 @@ def prefill_attention_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tenso
     rotated, quantised and stored, then the tile kernel converts the codes it loads to the 16-bit
     operands of its MFMAs.  A window split into several calls equals the whole window.  Returns
     [B, T, Hq*D]."""
-    if not prefill_attention_paged_kv8_supported(q, cos, k_pool, v_pool, table, pos, length, num_heads):
-        raise ValueError("prefill_attention_paged_kv8: unsupported shapes/dtypes/layout")
-    P, Hkv, D = _kv8_geometry(k_pool, v_pool)
-    B, NP = table.shape
-    T = q.shape[1]
+    return _prefill_paged(q, k, v, cos, sin, k_pool, v_pool, table, pos, length, num_heads, scale, True)
+
+
+def _check_window(name: str, q, k, v, cos, sin, num_heads: int, D: int) -> None:
+    """What every window launch (verify, prefill; contiguous or paged) asks of q / k / v [B, T, *] and sin
+    beyond its _supported predicate."""
     if q.shape[2] != num_heads * D:
-        raise ValueError("prefill_attention_paged_kv8: q width differs from num_heads * head_dim")
+        raise ValueError(f"{name}: q width differs from num_heads * head_dim")
     if sin.shape != cos.shape or sin.stride() != cos.stride() or sin.dtype != cos.dtype:
-        raise ValueError("prefill_attention_paged_kv8: sin must match cos")
+        raise ValueError(f"{name}: sin must match cos")
     if k.shape[:2] != q.shape[:2] or v.shape[:2] != q.shape[:2]:
-        raise ValueError("prefill_attention_paged_kv8: k/v must hold q's [B, T] rows")
-    if k.shape[2] != Hkv * D or v.shape[2] != Hkv * D:
-        raise ValueError("prefill_attention_paged_kv8: k/v width differs from the pools' heads")
+        raise ValueError(f"{name}: k/v must hold q's [B, T] rows")
+
+
+def _verify_rows(name: str, q, k, v, kv_width: int, owner: str):
+    """q / k / v [B, T, *] as the B T rows the verify launches take: unit inner stride, v in 4-B words.
+    `owner` names what k / v's width is checked against in the error text."""
+    R = q.shape[0] * q.shape[1]
+    q2, k2, v2 = (t.reshape(R, -1) for t in (q, k, v))
+    k2 = k2 if k2.stride(-1) == 1 else k2.contiguous()
+    q2 = q2 if q2.stride(-1) == 1 else q2.contiguous()
+    if v2.stride(-1) != 1 or v2.stride(0) % 2 or v2.data_ptr() % 4:
+        v2 = v2.contiguous()
+    if k2.shape[1] != kv_width or v2.shape[1] != kv_width:
+        raise ValueError(f"{name}: k/v width differs from the {owner} heads")
+    return q2, k2, v2
+
+
+def _prefill_rows(q, k, v, cos, sin, B: int, T: int, D: int):
+    """The row views of the prefill launches: (q, stride, k, stride, v, stride, cos, sin, their stride)."""
     q2, qs = _token_rows(q, B, T, 16, 8)
     k2, ks = _token_rows(k, B, T, 2, 1)
     v2, vs = _token_rows(v, B, T, 4, 2)
@@ -722,13 +661,7 @@ def prefill_attention_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tenso
     if ss != cs:
         s2, c2 = s2.contiguous(), c2.contiguous()
         cs = D
-    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
-    _lib.check(_lib.lib.qz_prefill_attention_paged_kv8(
-        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, NP, P, q2.data_ptr(), qs, k2.data_ptr(), ks, v2.data_ptr(),
-        vs, c2.data_ptr(), s2.data_ptr(), cs, k_pool.data_ptr(), v_pool.data_ptr(), table.data_ptr(), table.stride(0),
-        pos.data_ptr(), length.data_ptr(), out.data_ptr(), num_heads * D, float(scale), _lib.stream_of(q)),
-        "qz_prefill_attention_paged_kv8")
-    return out
+    return q2, qs, k2, ks, v2, vs, c2, s2, cs
 
 
 def _token_rows(t: torch.Tensor, B: int, T: int, align: int, mult: int):

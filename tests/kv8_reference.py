@@ -1,4 +1,4 @@
-"""The kv8 cache format restated on the CPU (numpy-free torch): what csrc/paged_attn_kv8.hip must write
+"""The kv8 cache format restated on the CPU (numpy-free torch): what csrc/paged_attn.hip must write
 and read back, bit for bit.  Importing it needs no GPU.
 
 A row -- one position of one kv head, D 16-bit elements of K (after the rotary) or of V -- becomes D OCP

@@ -1,4 +1,4 @@
-"""CPU: the budget of the kv8 attention kernels (csrc/paged_attn_kv8.hip), read from
+"""CPU: the budget of the kv8 attention kernels (csrc/paged_attn.hip), read from
 libquantizations.so's gfx950 code-object metadata in the manner of test_paged_kernel_resources.py:
 four instantiations of each (fp16 / bf16, D = 64 / 128), no scratch, no spills, no more LDS than the
 16-bit paged twin of the same dtype and head size, VGPR + AGPR <= 256, and no AGPRs outside the

@@ -633,6 +633,57 @@ int qz_logprobs_streams(const void *logits, int dtype, int B, int T, long long V
                         long long seq_row, long long seq_len, const long long *pos0, long long pos0_stride,
                         const long long *pos1, long long pos1_stride, int ntop, float *lp_tab, int *top_id_tab,
                         float *top_lp_tab, long long tab_row, void *work, void *stream);
+/* qz_constrain_logits / qz_constraint_advance: constrained decoding inside a step (csrc/constrain.hip).
+ *   A token-level automaton lives on the device in compressed form: class_of int16 [V] (token ->
+ *   equivalence class, tokens with identical transition columns share one), next int32 [S, C] (the
+ *   next state, negative = refused) and allow int32 [S, ceil(C/32)] (bit c & 31 of word c >> 5 is set
+ *   iff next[s, c] >= 0).  state int32 [B] holds each stream's state: -1 = unconstrained by request,
+ *   -2 = a refused transition was taken (qz_constraint_advance wrote it).
+ * qz_constrain_logits: in place on the 16-bit rows a pick reads, ONE launch in front of the pick and
+ *   behind qz_logits_process where both run (ceil(V/2048) workgroups of 256 threads per row; a thread
+ *   owns 8 tokens: one 16-B load of their classes, 16-B loads and stores of their logits; a vector is
+ *   stored only if one of its elements changed, so a row with nothing refused and no bias is never
+ *   stored).  logits [B*T, V] F16/BF16, row stride `row` >= V.  Three operands, each NULL = off:
+ *   1. the automaton (state; needs class_of, allow, next, S >= 1, C >= 1; tok int64 [B, T] as
+ *      qz_logits_process takes it, NULL allowed when T = 1).  Row (b, i) has the state s_i with
+ *      s_0 = state[b], s_i = next[s_{i-1}, class_of[tok[b, i]]], walked by the workgroup itself.  A
+ *      negative s_0, a state >= S, a draft outside [0, V) or a refused draft makes s_i negative from
+ *      there on, and the automaton then leaves the row as it is (such a row sits behind a draft the
+ *      row before it refuses: it is never accepted).  Otherwise every token whose class bit in
+ *      allow[s_i] is clear becomes -inf, a NaN logit included; an allowed logit keeps its bits.
+ *   2. the host mask (mask int32 [B, mask_row >= ceil(V/32)], xgrammar's layout: bit v & 31 of word
+ *      v >> 5 set = token v allowed; T must be 1).  Cleared bits become -inf; bits at or above V are
+ *      ignored.
+ *   3. the bias (bias_ids int32 [B, NB], bias_vals fp32 [B, NB], bias_n int32 [B]: stream b's list is
+ *      its first min(max(bias_n[b], 0), NB) entries and applies to all T rows of the stream, whatever
+ *      their state).  x' = round_dtype(fp32(x) + bias): one fp32 add, one rounding to nearest even.  A
+ *      NaN logit keeps its bits; a bias of -inf stores -inf (a ban); a bias of +inf or NaN is the
+ *      caller's error (a NaN entry is skipped).  Ids outside [0, V) are skipped; the ids of one list
+ *      must be distinct.
+ *   Order per element: the bias, then the masks -- a -inf of 1 or 2 wins.  Nothing but the first V
+ *   elements of a row is written.
+ *   QZ_ERR_ARG: NULL logits, a negative size, row < V, an automaton without class_of / allow / next
+ *   or with S or C of 0, T > 1 with an automaton and no tok, a mask with T > 1 or mask_row <
+ *   ceil(V/32), bias_ids without bias_vals / bias_n; QZ_ERR_DTYPE: not F16/BF16; QZ_ERR_SHAPE: T > 16,
+ *   B*T > 65535, V or S >= 2^31, C > 32767; B, T or V of 0, or every operand off, is QZ_OK with
+ *   nothing launched.
+ * qz_constraint_advance: ONE launch behind the pick, one wave per stream.  seq int64 [B, seq_row] is
+ *   the sequence itself, pos0 / pos1 int64 the streams' positions before and after the pick with
+ *   strides 0 (one shared position) or 1, as qz_logprobs_streams takes them.  For each emitted column
+ *   c = pos0[b] + 1 .. pos1[b] (inside [0, seq_len)): state[b] = next[state[b], class_of[seq[b, c]]].
+ *   A stream that emitted nothing keeps its state and is not written; a negative state (-1, -2) stays;
+ *   a refused transition, a token outside [0, V) or a state >= S writes -2 (it can only follow a
+ *   pick's fallback on a row that was -inf throughout).  Plain stores, no atomics, no workspace.
+ *   QZ_ERR_ARG: a NULL operand, a negative size, S or C of 0, seq_row < seq_len, a stride other than 0
+ *   or 1; QZ_ERR_SHAPE: B > 65535, V or S >= 2^31, C > 32767; B, V or seq_len of 0 is QZ_OK with
+ *   nothing launched. */
+int qz_constrain_logits(void *logits, int dtype, int B, int T, long long V, long long row, const int *state,
+                        const long long *tok, const short *class_of, const int *allow, const int *next, long long S,
+                        int C, const int *mask, long long mask_row, const int *bias_ids, const float *bias_vals,
+                        const int *bias_n, int NB, void *stream);
+int qz_constraint_advance(int *state, int B, const long long *seq, long long seq_row, long long seq_len,
+                          const long long *pos0, long long pos0_stride, const long long *pos1, long long pos1_stride,
+                          const short *class_of, const int *next, long long V, long long S, int C, void *stream);
 /* qz_gemv_dense: the model's fp16/bf16 lm_head for one decode token (transformers keeps it
  *   unquantised): y[m] = sum_k W[m*K + k] x[k] for m < M, fp32 accumulation, rounded once to
  *   dtype; K in {4096, 8192}, W and x 16-B aligned (else QZ_ERR_SHAPE, nothing launched). */

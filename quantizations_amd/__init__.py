@@ -31,7 +31,8 @@ from .generation import (  # noqa: F401
     prepare_for_decode,
     score,
 )
-from . import kv_pages  # noqa: F401
+from . import constraints, kv_pages  # noqa: F401
+from .constraints import TokenAutomaton  # noqa: F401
 from .kv_pages import KVPagePool, KVPagesExhausted  # noqa: F401
 
 __version__ = "0.1.0"

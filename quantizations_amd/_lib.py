@@ -140,6 +140,8 @@ SIGNATURES = {
     "qz_logprobs_work_bytes": [_ll, _ll, _i],
     "qz_token_logprobs": [_p, _i, _ll, _ll, _ll, _p, _i, _p, _p, _p, _p, _p],
     "qz_logprobs_streams": [_p, _i, _i, _i, _ll, _ll, _p, _ll, _ll, _p, _ll, _p, _ll, _i, _p, _p, _p, _ll, _p, _p],
+    "qz_constrain_logits": [_p, _i, _i, _i, _ll, _ll, _p, _p, _p, _p, _p, _ll, _i, _p, _ll, _p, _p, _p, _i, _p],
+    "qz_constraint_advance": [_p, _i, _p, _ll, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _ll, _i, _p],
     "qz_rope_table": [_i, _i, _i, _i, _p, _ll, _ll, _p, _p, _ll, _p, _f, _p, _p, _p],
     "qz_add_rmsnorm": [_p, _p, _i, _ll, _i, _ll, _p, _f, _p, _p, _ll, _p],
     "qz_bench_read_floor": [_p, _ll, _p, _p],

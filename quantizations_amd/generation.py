@@ -12,7 +12,10 @@ same tokens in fewer reads of the weights -- greedy, or with sample=True / promp
 the tokens each position's uniform number draws.  set_penalties() / repetition_penalty=,
 presence_penalty=, frequency_penalty=, no_repeat_ngram_size=, min_new_tokens= put
 layer_ops.process_logits in front of every pick, inside the captured step: the processors read each
-stream's history and their own parameters on the device.  One GPU only; no beams.
+stream's history and their own parameters on the device.  constraint= (a constraints.TokenAutomaton),
+logit_bias= / set_logit_bias() and set_token_mask() put layer_ops.constrain_logits behind it and
+layer_ops.constraint_advance behind the pick: each stream's automaton state lives on the device and
+follows the emitted tokens, drafts included.  One GPU only; no beams.
 """
 from __future__ import annotations
 
@@ -107,6 +110,65 @@ def _logprob_buffers(sess, logprobs, who: str) -> None:
     sess._pos0 = torch.zeros_like(sess.pos)
 
 
+def _constraint_buffers(sess, constraint, logit_bias_slots, who: str) -> None:
+    """The device state of constrained decoding: the automaton's tables and a state per
+    stream when the session was opened with `constraint`, bias lists of `logit_bias_slots` entries per
+    stream, and the host mask once set_token_mask() made one.  Without any of them no buffer exists and
+    every hook below returns at once."""
+    from .constraints import TokenAutomaton
+
+    B, dev = sess.batch, sess.device
+    sess.vocab = int(sess.model.config.vocab_size)
+    sess.constraint, sess._cn, sess.constraint_state = constraint, None, None
+    if constraint is not None:
+        if not isinstance(constraint, TokenAutomaton):
+            raise ValueError(f"{who}: constraint must be a TokenAutomaton")
+        if constraint.V != sess.vocab:
+            raise ValueError(f"{who}: the automaton is over {constraint.V} tokens, the model over {sess.vocab}")
+        sess._cn = constraint.to(dev)
+        sess.constraint_state = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        if sess._pos0 is None:
+            sess._pos0 = torch.zeros_like(sess.pos)   # the snapshot the log-probabilities take, shared
+    nb = int(logit_bias_slots or 0)
+    if nb < 0:
+        raise ValueError(f"{who}: logit_bias_slots must not be negative")
+    sess.logit_bias_slots = nb
+    sess._bias_ids = sess._bias_vals = sess._bias_n = sess._token_mask = None
+    if nb:
+        sess._bias_ids = torch.zeros((B, nb), dtype=torch.int32, device=dev)
+        sess._bias_vals = torch.zeros((B, nb), dtype=torch.float32, device=dev)
+        sess._bias_n = torch.zeros(B, dtype=torch.int32, device=dev)
+    sess._bias_count = [0] * B     # host knowledge of bias_n
+    # host knowledge: the step holds constrain_logits (with every operand that exists by then)
+    sess._constraining = constraint is not None
+
+
+def _given_bias(logit_bias, suppress_tokens, batch: int, who: str):
+    """generate()'s logit_bias (a dict, or one per stream) and suppress_tokens (ids, -inf for every
+    stream) as one dict per stream, or None when neither was given."""
+    if logit_bias is None and suppress_tokens is None:
+        return None
+    if logit_bias is None:
+        per = [{} for _ in range(batch)]
+    elif hasattr(logit_bias, "items"):
+        per = [dict(logit_bias) for _ in range(batch)]
+    else:
+        per = [dict(d or {}) for d in logit_bias]
+        if len(per) != batch:
+            raise ValueError(f"{who}: logit_bias is one dict or one per stream ({batch}), got {len(per)}")
+    for t in ([] if suppress_tokens is None else suppress_tokens):
+        for d in per:
+            d[int(t)] = float("-inf")
+    return per
+
+
+def _open_constraints(sess, bias) -> None:
+    """generate()'s part after the session is open: the bias lists."""
+    if bias is not None:
+        for b, d in enumerate(bias):
+            sess.set_logit_bias(b, d)
+
+
 class GenerateOutput(NamedTuple):
     """What generate() / generate_ragged() return when `logprobs` is given: tensors for generate(), one
     tensor per prompt for generate_ragged().  logprobs[.., c] is the log-probability of sequences[.., c]
@@ -133,9 +195,19 @@ class DecodeSession:
     [B, max_len, n], aligned with hist -- entry [b, c] describes token hist[b, c], NaN / -1 where there
     is none (prompt columns, columns not reached).  The model's own distribution: the log-softmax of
     the lm_head row before penalties, temperature, top-k and top-p.  One layer_ops.logprobs_streams
-    call follows every pick, inside the captured step; the tokens are those of the session without."""
+    call follows every pick, inside the captured step; the tokens are those of the session without.
 
-    def __init__(self, model, batch: int, max_len: int, *, graph: bool = True, logprobs: Optional[int] = None):
+    constraint (a constraints.TokenAutomaton; None: off -- no buffer, launch or graph node) keeps every
+    stream's output inside the automaton: `constraint_state` int32 [B] is each stream's state (-1:
+    unconstrained, -2: a refused token was taken), prefill(constraint_start=) sets it, one
+    layer_ops.constrain_logits call in front of every pick (behind the penalties) turns the logits of the
+    tokens the state refuses into -inf, one layer_ops.constraint_advance call behind it moves the state
+    over the picked token -- both inside the captured step, no host work per replay.
+    logit_bias_slots = NB makes room for NB bias entries per stream (set_logit_bias), set_token_mask()
+    takes a host-computed bitmask; both ride in the same launch."""
+
+    def __init__(self, model, batch: int, max_len: int, *, graph: bool = True, logprobs: Optional[int] = None,
+                 constraint=None, logit_bias_slots: int = 0):
         from transformers.cache_utils import StaticCache
 
         if batch < 1 or max_len < 1:
@@ -170,6 +242,7 @@ class DecodeSession:
         self._prefilled = False
         self._next = 0   # tokens in hist (host copy of pos + 1)
         _logprob_buffers(self, logprobs, "DecodeSession")
+        _constraint_buffers(self, constraint, logit_bias_slots, "DecodeSession")
 
     def set_sampling(self, temperature=None, top_k=None, top_p=None) -> None:
         """Scalars or one value per stream, written in place: the next step, replayed or not, uses
@@ -245,10 +318,12 @@ class DecodeSession:
         """In front of a pick, in a session with `logprobs`: snapshot pos and return the rows the
         log-probabilities are read from -- the logits themselves, or a copy of them when a processing
         launch is about to rewrite them in place (B T V 16-bit elements, one captured copy)."""
+        if self._pos0 is None:
+            return None
+        self._pos0.copy_(self.pos)       # shared with constraint_advance: a constrained session has one too
         if self._lp_n is None:
             return None
-        self._pos0.copy_(self.pos)
-        return logits.clone() if self._processing else logits
+        return logits.clone() if (self._processing or self._constraining) else logits
 
     def _record(self, raw: Optional[torch.Tensor], rows: slice = slice(None), T: int = 1) -> None:
         """Behind a pick: the log-probabilities of the tokens it emitted (columns pos0 + 1 .. pos of
@@ -269,19 +344,127 @@ class DecodeSession:
             self.top_ids[b] = -1
             self.top_logprobs[b] = float("nan")
 
+    def set_logit_bias(self, b, bias) -> None:
+        """Stream b's logit bias ({token id: bias}; b None: every stream), copied in place into the
+        session's bias lists (logit_bias_slots entries per stream), so the next step, replayed or not,
+        uses it.  A bias is finite or -inf (a ban); an empty dict clears the list.  The bias is added to
+        the stream's logits in front of every pick, behind the penalties; `logprobs` stay the model's
+        own.  A step captured with no constraint, bias or mask holds no launch for it: a bias cannot be
+        switched on after that capture."""
+        from .constraints import bias_row
+
+        ids, vals = bias_row(bias, self.vocab)
+        rows = range(self.batch) if b is None else [int(b)]
+        if any(not 0 <= r < self.batch for r in rows):
+            raise ValueError(f"set_logit_bias: stream {b} outside 0..{self.batch - 1}")
+        if len(ids) > self.logit_bias_slots:
+            raise ValueError(f"set_logit_bias: {len(ids)} entries, the session was opened with logit_bias_slots="
+                             f"{self.logit_bias_slots}")
+        if ids and self._graph is not None and not self._constraining:
+            raise ValueError("set_logit_bias: this session captured a step without constrained decoding")
+        if not self.logit_bias_slots:
+            return
+        n = len(ids)
+        for r in rows:
+            if n:
+                self._bias_ids[r, :n] = torch.tensor(ids, dtype=torch.int32, device=self.device)
+                self._bias_vals[r, :n] = torch.tensor(vals, dtype=torch.float32, device=self.device)
+            self._bias_n[r] = n
+            self._bias_count[r] = n
+        if self._graph is None:
+            self._constraining = self._cn is not None or self._token_mask is not None or any(self._bias_count)
+
+    def set_token_mask(self, mask) -> None:
+        """A host-computed bitmask for the next picks (int32 [B, ceil(V/32)], xgrammar's layout: bit
+        v & 31 of word v >> 5 set = token v allowed), copied in place, so a replay follows it; None
+        allows everything again.  The first call makes the buffer, which has to happen before the step
+        is captured.  A SpeculativeSession refuses it: the mask of a window's row i would depend on
+        drafts chosen on the device."""
+        if hasattr(self, "T"):
+            raise ValueError("set_token_mask: a host mask describes one row per stream; SpeculativeSession verifies a "
+                             "window per stream (use a TokenAutomaton)")
+        words = (self.vocab + 31) // 32
+        if mask is None:
+            if self._token_mask is not None:
+                self._token_mask.fill_(-1)
+            return
+        m = torch.as_tensor(mask)
+        if m.dtype != torch.int32 or m.shape != (self.batch, words):
+            raise ValueError(f"set_token_mask: mask must be int32 [{self.batch}, {words}]")
+        if self._token_mask is None:
+            if self._graph is not None:
+                raise ValueError("set_token_mask: this session captured a step without a host mask")
+            self._token_mask = torch.full((self.batch, words), -1, dtype=torch.int32, device=self.device)
+            self._constraining = True
+        self._token_mask.copy_(m)
+
+    def _constrain(self, logits: torch.Tensor, rows: slice = slice(None), tok: Optional[torch.Tensor] = None,
+                   T: int = 1) -> None:
+        """layer_ops.constrain_logits in front of a pick and behind _process, when a constraint, a bias or
+        a mask is on: in place on the rows the pick reads."""
+        if not self._constraining:
+            return
+        r = rows
+        auto = self._cn is not None
+        _ops.constrain_logits(logits, state=self.constraint_state[r] if auto else None, tok=tok if auto else None,
+                              automaton=self._cn, mask=None if self._token_mask is None else self._token_mask[r],
+                              bias_ids=None if self._bias_ids is None else self._bias_ids[r],
+                              bias_vals=None if self._bias_ids is None else self._bias_vals[r],
+                              bias_n=None if self._bias_ids is None else self._bias_n[r], T=T)
+
+    def _advance(self, rows: slice = slice(None)) -> None:
+        """Behind a pick (and _record): the automaton states follow the tokens it emitted, columns
+        pos0 + 1 .. pos of hist."""
+        if self._cn is None:
+            return
+        r = rows
+        one = self.pos.numel() == 1
+        _ops.constraint_advance(self.constraint_state[r], self.hist[r], self._pos0 if one else self._pos0[r],
+                                self.pos if one else self.pos[r], self._cn)
+
+    def _cn_state(self) -> list:
+        """What the advance writes: a capture's warm-up runs move it, _capture() puts it back."""
+        return [] if self._cn is None else [self.constraint_state]
+
+    def _cn_start(self, rows, start, who: str, keep: bool = False) -> None:
+        """Write the automaton state of the streams `rows` in front of their first pick: `start` is an
+        int or one per stream (-1: unconstrained); None is the automaton's start state, or with `keep`
+        the state the stream has."""
+        rows = list(rows)
+        if self._cn is None:
+            if start is not None:
+                raise ValueError(f"{who}: constraint_start needs a session opened with constraint=")
+            return
+        if start is None:
+            if keep:
+                return
+            start = self.constraint.starts[0] if self.constraint.starts else 0
+        vals = [int(v) for v in torch.as_tensor(start).reshape(-1).tolist()]
+        if len(vals) == 1:
+            vals = vals * len(rows)
+        if len(vals) != len(rows) or any(not -1 <= v < self.constraint.S for v in vals):
+            raise ValueError(f"{who}: constraint_start is one state or one per stream, each -1 or in "
+                             f"0..{self.constraint.S - 1}")
+        self.constraint_state[rows] = torch.tensor(vals, dtype=torch.int32, device=self.device)
+
     def _pick(self, logits: torch.Tensor) -> None:
         raw = self._raw_rows(logits)
         self._process(logits)
+        self._constrain(logits)
         if self._greedy_only and logits.is_cuda:
             _ops.greedy_step(logits, self._hist_next, self.pos, self.tok)
         else:
             _ops.sample_step(logits, self._hist_next, self.pos, self.tok, self.temperature, self.top_k, self.top_p,
                              self._uniform_full)
         self._record(raw)
+        self._advance()
 
     @torch.inference_mode()
-    def prefill(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> None:
-        """Run the prompts ([B, S], equal lengths) and pick each stream's first new token."""
+    def prefill(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, *,
+                constraint_start=None) -> None:
+        """Run the prompts ([B, S], equal lengths) and pick each stream's first new token.
+        constraint_start (sessions opened with constraint=): the automaton state each stream starts in,
+        one for all or one per stream; -1 leaves a stream unconstrained; None is the automaton's start."""
         if attention_mask is not None and not bool(attention_mask.bool().all()):
             raise ValueError("DecodeSession.prefill: padded prompts are not supported (attention_mask holds a zero)")
         if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
@@ -291,6 +474,7 @@ class DecodeSession:
             raise ValueError("DecodeSession.prefill: the prompt must be shorter than max_len")
         if self._prefilled:
             raise ValueError("DecodeSession.prefill: a session takes one prompt; open another for the next")
+        self._cn_start(range(self.batch), constraint_start, "DecodeSession.prefill")
         ids = input_ids.to(self.device)
         self.hist[:, :S] = ids
         self.pos.fill_(S - 1)                          # the last prompt token; the pick makes it S
@@ -318,7 +502,7 @@ class DecodeSession:
         # two warm-up runs on a side stream, as the benchmark does; they advance the cache lengths,
         # pos, tok and hist, which are put back so that no position is consumed (the keys and values
         # they wrote lie past the restored length: masked now, overwritten by the steps that follow)
-        state = [self.tok, self.pos, self._hist_full] + self._cache_lengths() + self._lp_state()
+        state = [self.tok, self.pos, self._hist_full] + self._cache_lengths() + self._lp_state() + self._cn_state()
         saved = [t.clone() for t in state]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -360,7 +544,8 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
              prompt_lookup_num_tokens: Optional[int] = None,
              max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False,
              repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
-             no_repeat_ngram_size=None, min_new_tokens=None, logprobs: Optional[int] = None):
+             no_repeat_ngram_size=None, min_new_tokens=None, logprobs: Optional[int] = None,
+             constraint=None, constraint_start=None, logit_bias=None, suppress_tokens=None):
     """input_ids [B, S] (equal-length prompts) followed by up to max_new_tokens picked tokens per
     stream: greedy, or with do_sample temperature / top_k / top_p (scalars or one per stream; a
     temperature <= 0 keeps that stream greedy) drawn from `generator` (a torch.Generator or a seed).
@@ -380,7 +565,11 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
     logprobs (None: off; 0: the chosen tokens only; 1..20: that many top entries as well): return a
     GenerateOutput(sequences, logprobs [B, S + new], top_ids / top_logprobs [B, S + new, n]) aligned
     with the sequences -- the model's own log-softmax, before penalties, temperature, top-k and top-p;
-    NaN / -1 on the prompt columns and behind a stream's EOS."""
+    NaN / -1 on the prompt columns and behind a stream's EOS.
+    constraint (a TokenAutomaton) with constraint_start (a state, or one per stream; -1: that stream is
+    unconstrained; None: the automaton's start): every pick is masked by its stream's state inside the
+    step, with or without prompt lookup.  logit_bias ({token id: bias}, or one dict per stream; -inf
+    bans) and suppress_tokens (ids banned for every stream) are added in front of every pick."""
     if input_ids.dim() != 2:
         raise ValueError("generate: input_ids must be [B, S]")
     _check_logprobs(logprobs, "generate")
@@ -399,11 +588,18 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
                               torch.full((B, S, logprobs), float("nan"), device=dev))
     penalties = _given_penalties(repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size,
                                  min_new_tokens)
+    bias = _given_bias(logit_bias, suppress_tokens, B, "generate")
+    if constraint is None and constraint_start is not None:
+        raise ValueError("generate: constraint_start needs constraint")
+    slots = max((len(d) for d in bias), default=0) if bias is not None else 0
     if prompt_lookup_num_tokens is not None:
         sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator) if do_sample else None
         return _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attention_mask, graph,
-                                     prompt_lookup_num_tokens, max_matching_ngram_size, sampling, penalties, logprobs)
-    sess = DecodeSession(model, B, S + max_new_tokens, graph=graph, logprobs=logprobs)
+                                     prompt_lookup_num_tokens, max_matching_ngram_size, sampling, penalties, logprobs,
+                                     constraint, constraint_start, bias)
+    sess = DecodeSession(model, B, S + max_new_tokens, graph=graph, logprobs=logprobs, constraint=constraint,
+                         logit_bias_slots=slots)
+    _open_constraints(sess, bias)
     if penalties:
         sess.set_penalties(**penalties)
         if eos_token_id is not None:
@@ -411,7 +607,7 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
     if do_sample:
         sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
         sess.seed(generator)
-    sess.prefill(input_ids, attention_mask)        # writes hist[:, S]
+    sess.prefill(input_ids, attention_mask, constraint_start=constraint_start)        # writes hist[:, S]
     n = 1
     while n < max_new_tokens:
         sess.step()
@@ -554,11 +750,17 @@ class StreamSession:
     fill the prompt columns 1..S-1 too, the lm_head and layer_ops.token_logprobs over
     PROMPT_LOGPROBS_SLAB window rows at a time (the logits scratch is that many rows x V, never B S x V).
     Column 0 stays NaN, and so do the columns of pages mapped from the prefix cache (no forward ran
-    there) and the first column behind them."""
+    there) and the first column behind them.
+
+    constraint / logit_bias_slots: DecodeSession's, per stream: prefill(), admit() and extend() take
+    constraint_start (admit under a captured graph follows it without recapture; extend's None keeps the
+    state, and the appended tokens do not advance it), fork(src, dst) copies the state, and a stream
+    that is not live keeps its state."""
 
     def __init__(self, model, batch: int, max_len: int, *, graph: bool = True, prefill_chunk: Optional[int] = None,
                  kv_pages: Optional[int] = None, prefix_cache: bool = False, kv_dtype: Optional[str] = None,
-                 logprobs: Optional[int] = None, prompt_logprobs: bool = False):
+                 logprobs: Optional[int] = None, prompt_logprobs: bool = False, constraint=None,
+                 logit_bias_slots: int = 0):
         _check_kv_dtype(kv_dtype, "StreamSession", kv_pages)
         _check_logprobs(logprobs, "StreamSession")
         if prompt_logprobs and prefill_chunk is None:
@@ -620,6 +822,7 @@ class StreamSession:
         self._prefilled = False
         self.prompt_logprobs = bool(prompt_logprobs)
         _logprob_buffers(self, logprobs, "StreamSession")
+        _constraint_buffers(self, constraint, logit_bias_slots, "StreamSession")
 
     set_sampling = DecodeSession.set_sampling
     set_penalties = DecodeSession.set_penalties
@@ -629,11 +832,18 @@ class StreamSession:
     _record = DecodeSession._record
     _lp_state = DecodeSession._lp_state
     _lp_reset = DecodeSession._lp_reset
+    set_logit_bias = DecodeSession.set_logit_bias
+    set_token_mask = DecodeSession.set_token_mask
+    _constrain = DecodeSession._constrain
+    _advance = DecodeSession._advance
+    _cn_state = DecodeSession._cn_state
+    _cn_start = DecodeSession._cn_start
 
     def _pick(self, logits: torch.Tensor, rows: slice = slice(None)) -> None:
         r = rows
         raw = self._raw_rows(logits)
         self._process(logits, r)
+        self._constrain(logits, r)
         if self._greedy_only:
             _ops.greedy_step_streams(logits, self._hist_next[r], self.pos[r], self.live[r], self.stop[r],
                                      self.limit[r], self.tok[r])
@@ -642,6 +852,7 @@ class StreamSession:
                                      self.limit[r], self.tok[r], self.temperature[r], self.top_k[r], self.top_p[r],
                                      self._uniform_full[r])
         self._record(raw, r)
+        self._advance(r)
 
     def _limit_of(self, length: int, max_new_tokens: Optional[int]) -> int:
         room = self.max_len - length
@@ -734,7 +945,8 @@ class StreamSession:
         return self.model.get_output_embeddings()(hidden.unsqueeze(1))[:, 0]
 
     @torch.inference_mode()
-    def prefill(self, input_ids: torch.Tensor, lengths, *, stop=None, max_new_tokens=None, prefix_salt=None) -> None:
+    def prefill(self, input_ids: torch.Tensor, lengths, *, stop=None, max_new_tokens=None, prefix_salt=None,
+                constraint_start=None) -> None:
         """Run right-padded prompts (input_ids [B, Smax], stream b's prompt in its first lengths[b]
         columns) in one forward under the ordinary causal mask -- a real token never sees the pad to
         its right -- and pick each stream's first new token from the logits at lengths[b] - 1.  The
@@ -742,7 +954,9 @@ class StreamSession:
         overwritten as the stream grows.  stop: a token id per stream or one for all (None / -1:
         none); max_new_tokens likewise (None: up to max_len).  kv_pages: every stream's pages are
         reserved first (KVPagesExhausted: nothing was changed), and with prefix_cache each prompt's
-        full pages are published afterwards under prefix_salt."""
+        full pages are published afterwards under prefix_salt.
+        constraint_start (sessions opened with constraint=): the automaton state each stream starts in,
+        one for all or one per stream; -1 leaves a stream unconstrained; None is the automaton's start."""
         if self._prefilled:
             raise ValueError("StreamSession.prefill: a session is prefilled once; admit() replaces single streams")
         if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
@@ -764,6 +978,7 @@ class StreamSession:
                 for b in range(B):
                     self.pages.release(b)
                 raise
+        self._cn_start(range(B), constraint_start, "StreamSession.prefill")
         ids = input_ids.to(dev)
         ln = torch.tensor(lens, device=dev)
         real = torch.arange(Smax, device=dev)[None, :] < ln[:, None]
@@ -789,7 +1004,7 @@ class StreamSession:
 
     @torch.inference_mode()
     def admit(self, b: int, prompt: torch.Tensor, *, stop: Optional[int] = None,
-              max_new_tokens: Optional[int] = None, prefix_salt=None) -> None:
+              max_new_tokens: Optional[int] = None, prefix_salt=None, constraint_start=None) -> None:
         """Replace stream b by a new prompt (1-D) while the other streams keep their state: the
         prompt runs eagerly at batch 1 into a scratch StaticCache, its keys and values [:S] are copied
         into row b of every layer, and hist[b], pos[b], stop[b], limit[b], live[b] and the stream's
@@ -802,7 +1017,9 @@ class StreamSession:
         (S - 1) // 128, the last prompt token must run -- are mapped into row b and the windows start
         behind them; the prompt's own new full pages are published afterwards.  prefix_salt keeps
         prompts apart whose keys differ for equal tokens (streams on different adapters pass different
-        salts); with an adapter bank on the model and no salt, the call shares nothing."""
+        salts); with an adapter bank on the model and no salt, the call shares nothing.
+        constraint_start: the new stream's automaton state (-1: unconstrained; None: the automaton's
+        start), written like the rest of its state, so the captured step follows it."""
         from transformers.cache_utils import StaticCache
 
         if not self._prefilled:
@@ -815,6 +1032,8 @@ class StreamSession:
         limit = self._limit_of(S, max_new_tokens)
         dev = self.device
         ids = prompt.to(dev).view(1, S)
+        if self._cn is None and constraint_start is not None:
+            raise ValueError("StreamSession.admit: constraint_start needs a session opened with constraint=")
         if self.prefill_chunk is not None:
             start, salt = 0, False
             if self.pages is not None:
@@ -825,6 +1044,7 @@ class StreamSession:
             self._lp_reset(b)
             hidden = self._windows(ids[:, start:], [S - start], b, start)
             self._set_stream(b, ids[0], 0, S, stop, limit)
+            self._cn_start([b], constraint_start, "StreamSession.admit")
             self._pick(self._head(hidden), slice(b, b + 1))
             if salt is not False:
                 self.pages.register(b, ids[0], S // _ops.KV_PAGE, salt, final_below=S)
@@ -845,6 +1065,7 @@ class StreamSession:
         self.stop[b] = -1 if stop is None else int(stop)
         self.limit[b] = limit
         self.live[b] = 1    # before the pick, which writes live streams only and may retire this one at once
+        self._cn_start([b], constraint_start, "StreamSession.admit")
         self._pick(out.logits[:, -1], slice(b, b + 1))
 
     def _set_stream(self, b: int, tokens: torch.Tensor, at: int, end: int, stop, limit: int) -> None:
@@ -858,7 +1079,7 @@ class StreamSession:
 
     @torch.inference_mode()
     def extend(self, b: int, tokens: torch.Tensor, *, stop: Optional[int] = None,
-               max_new_tokens: Optional[int] = None) -> None:
+               max_new_tokens: Optional[int] = None, constraint_start=None) -> None:
         """Append tokens (1-D) to stream b's sequence, live or retired -- a conversation's next turn --
         and pick the token after them.  hist[b, pos[b]], the stream's newest token, is not in the cache
         yet: the window is that token followed by `tokens`, at positions pos[b] .., in chunks of
@@ -868,7 +1089,9 @@ class StreamSession:
         all -- and stop / limit / live are set as admit() sets them.  The whole sequence so far, the appended
         tokens and the tokens generated before them included, counts as prompt from here on: the
         presence and frequency penalties count what is generated after this call, and min_new_tokens
-        starts again.  The other streams keep their state; no recapture."""
+        starts again.  The other streams keep their state; no recapture.
+        constraint_start: None keeps the stream's automaton state (the appended tokens do not advance
+        it), a state or -1 replaces it in front of the pick."""
         if self.prefill_chunk is None:
             raise ValueError("StreamSession.extend: open the session with prefill_chunk (the prefill attention "
                              "places the window)")
@@ -889,6 +1112,7 @@ class StreamSession:
         ids = torch.cat((self._hist_full[b, p:p + 1], new)).view(1, n + 1)
         hidden = self._windows(ids, [n + 1], b, p)
         self._set_stream(b, new, p + 1, p + 1 + n, stop, limit)
+        self._cn_start([b], constraint_start, "StreamSession.extend", keep=True)
         self._pick(self._head(hidden), slice(b, b + 1))
 
     def _need_pages(self, who: str) -> None:
@@ -932,6 +1156,8 @@ class StreamSession:
         self._hist_full[dst].copy_(self._hist_full[src])
         for t in self._lp_state()[:3]:
             t[dst].copy_(t[src])
+        for t in self._cn_state():
+            t[dst].copy_(t[src])
         self.tok[dst].copy_(self.tok[src])
         if hasattr(self, "pos_ids"):
             self.pos_ids[dst].copy_(self.pos_ids[src])
@@ -955,7 +1181,7 @@ class StreamSession:
 
     def _step_state(self) -> list:
         """What a step writes besides the cache: _capture() puts it back after its warm-up runs."""
-        return [self.tok, self.pos, self.live, self._hist_full] + self._lp_state()
+        return [self.tok, self.pos, self.live, self._hist_full] + self._lp_state() + self._cn_state()
 
     def _capture(self) -> None:
         # two warm-up runs on a side stream, then the capture; each advances the live streams, which
@@ -1033,12 +1259,17 @@ class SpeculativeSession(StreamSession):
 
     set_penalties(): the processors run over all B T rows in one launch before the pick, row i with the
     history hist[b, :pos[b] + 1] followed by the drafts 1..i.  An emitted row's drafts are the tokens
-    emitted before it, so its history is the real one and the tokens stay StreamSession's."""
+    emitted before it, so its history is the real one and the tokens stay StreamSession's.
+
+    constraint: the one constrain_logits launch covers the B T rows, row i masked by the state reached
+    from the stream's over the drafts 1..i (walked on the device); a row behind a draft that the row in
+    front of it refuses is left alone and is never accepted, and the advance follows the accepted tokens.
+    The tokens stay StreamSession's under the same automaton.  set_token_mask() raises here."""
 
     def __init__(self, model, batch: int, max_len: int, *, draft_tokens: int = 3, ngram: int = 3, graph: bool = True,
                  sample: bool = False, prefill_chunk: Optional[int] = None, kv_pages: Optional[int] = None,
                  prefix_cache: bool = False, kv_dtype: Optional[str] = None, logprobs: Optional[int] = None,
-                 prompt_logprobs: bool = False):
+                 prompt_logprobs: bool = False, constraint=None, logit_bias_slots: int = 0):
         from .core import MT_MAX_TOKENS
 
         if int(draft_tokens) < 1:
@@ -1051,7 +1282,7 @@ class SpeculativeSession(StreamSession):
                              f"multi-token kernels take {MT_MAX_TOKENS}")
         super().__init__(model, batch, max_len, graph=graph, prefill_chunk=prefill_chunk, kv_pages=kv_pages,
                          prefix_cache=prefix_cache, kv_dtype=kv_dtype, logprobs=logprobs,
-                         prompt_logprobs=prompt_logprobs)
+                         prompt_logprobs=prompt_logprobs, constraint=constraint, logit_bias_slots=logit_bias_slots)
         dev = self.device
         self.T, self.ngram, self.sample = T, int(ngram), bool(sample)
         self.tok = torch.zeros((batch, T), dtype=torch.int64, device=dev)
@@ -1079,6 +1310,7 @@ class SpeculativeSession(StreamSession):
         r = rows
         raw = self._raw_rows(logits)
         self._process(logits, r)
+        self._constrain(logits, r)
         first = self.tok[r, :1].contiguous()
         if self._greedy_only:
             _ops.greedy_step_streams(logits, self._hist_next[r], self.pos[r], self.live[r], self.stop[r],
@@ -1089,6 +1321,7 @@ class SpeculativeSession(StreamSession):
                                      self._uniform_full[r])
         self.tok[r, :1] = first
         self._record(raw, r)
+        self._advance(r)
         self._draft()
 
     def _step(self) -> None:
@@ -1097,6 +1330,7 @@ class SpeculativeSession(StreamSession):
         lo = lo.reshape(self.batch * self.T, -1)
         raw = self._raw_rows(lo)
         self._process(lo, tok=self.tok)    # row i sees the drafts 1..i it was fed after
+        self._constrain(lo, tok=self.tok, T=self.T)   # row i in the state reached over the drafts 1..i
         if self._greedy_only:
             _ops.verify_step_streams(lo, self._hist_next, self.pos, self.live, self.stop, self.limit, self.tok,
                                      self.accepted)
@@ -1105,6 +1339,7 @@ class SpeculativeSession(StreamSession):
                                             self.accepted, self.temperature, self.top_k, self.top_p,
                                             self._uniform_full)
         self._record(raw, T=self.T)        # the accepted rows: columns pos0 + 1 .. pos
+        self._advance()                    # the states follow the accepted tokens
         self._tokens.add_(self.accepted)
         self._steps.add_(self.accepted.ne(0))
         self._draft()
@@ -1121,14 +1356,16 @@ class SpeculativeSession(StreamSession):
 def _speculative_session(model, batch: int, max_len: int, prompt_lookup_num_tokens, max_matching_ngram_size,
                          do_sample: bool, graph: bool, who: str, sampling: bool = False,
                          prefill_chunk: Optional[int] = None, kv_pages: Optional[int] = None,
-                         kv_dtype: Optional[str] = None, logprobs: Optional[int] = None) -> SpeculativeSession:
+                         kv_dtype: Optional[str] = None, logprobs: Optional[int] = None, constraint=None,
+                         logit_bias_slots: int = 0) -> SpeculativeSession:
     if do_sample and not sampling:
         raise ValueError(f"{who}: prompt_lookup_num_tokens verifies drafts against the greedy token; "
                          "do_sample is not supported with it unless prompt_lookup_sampling=True")
     n = PROMPT_LOOKUP_NGRAM if max_matching_ngram_size is None else int(max_matching_ngram_size)
     return SpeculativeSession(model, batch, max_len, draft_tokens=int(prompt_lookup_num_tokens), ngram=n, graph=graph,
                               sample=bool(do_sample and sampling), prefill_chunk=prefill_chunk, kv_pages=kv_pages,
-                              kv_dtype=kv_dtype, logprobs=logprobs)
+                              kv_dtype=kv_dtype, logprobs=logprobs, constraint=constraint,
+                              logit_bias_slots=logit_bias_slots)
 
 
 def _run_speculative(sess: SpeculativeSession, max_new_tokens: int) -> None:
@@ -1141,7 +1378,7 @@ def _run_speculative(sess: SpeculativeSession, max_new_tokens: int) -> None:
 
 def _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attention_mask, graph,
                           prompt_lookup_num_tokens, max_matching_ngram_size, sampling=None,
-                          penalties=None, logprobs=None):
+                          penalties=None, logprobs=None, constraint=None, constraint_start=None, bias=None):
     """generate()'s result from a SpeculativeSession: every stream runs to its EOS or to max_new_tokens,
     then the rows are laid out as the plain loop leaves them -- S + n columns, n the first multiple of
     STOP_CHECK_EVERY by which every stream had its EOS (max_new_tokens if there is none), each
@@ -1151,13 +1388,17 @@ def _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attent
         raise ValueError("generate: padded prompts are not supported (attention_mask holds a zero)")
     B, S = input_ids.shape
     sess = _speculative_session(model, B, S + max_new_tokens, prompt_lookup_num_tokens, max_matching_ngram_size,
-                                sampling is not None, graph, "generate", sampling is not None, logprobs=logprobs)
+                                sampling is not None, graph, "generate", sampling is not None, logprobs=logprobs,
+                                constraint=constraint,
+                                logit_bias_slots=max((len(d) for d in bias), default=0) if bias is not None else 0)
+    _open_constraints(sess, bias)
     if sampling is not None:
         sess.set_sampling(temperature=sampling["temperature"], top_k=sampling["top_k"], top_p=sampling["top_p"])
         sess.seed(sampling["generator"])
     if penalties:
         sess.set_penalties(**penalties)
-    sess.prefill(input_ids, [S] * B, stop=eos_token_id, max_new_tokens=max_new_tokens)
+    sess.prefill(input_ids, [S] * B, stop=eos_token_id, max_new_tokens=max_new_tokens,
+                 constraint_start=constraint_start)
     _run_speculative(sess, max_new_tokens)
     seqs = sess.sequences()
     n = max_new_tokens
@@ -1182,7 +1423,8 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
                     max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False,
                     repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
                     no_repeat_ngram_size=None, min_new_tokens=None, prefill_chunk: Optional[int] = None,
-                    kv_pages: Optional[int] = None, kv_dtype: Optional[str] = None, logprobs: Optional[int] = None):
+                    kv_pages: Optional[int] = None, kv_dtype: Optional[str] = None, logprobs: Optional[int] = None,
+                    constraint=None, constraint_start=None, logit_bias=None, suppress_tokens=None):
     """generate() for prompts of different lengths: `prompts` are 1-D int64 tensors; returns one 1-D
     int64 tensor per prompt on the model's device, the prompt followed by up to max_new_tokens picked
     tokens of its own, ending with eos_token_id if the stream picked it.  A stream that stopped writes
@@ -1200,7 +1442,9 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     Smax + max_new_tokens positions per prompt (needs prefill_chunk).
     kv_dtype: the session's: "fp8" keeps the pages as kv8 rows (needs kv_pages).
     logprobs: as generate() takes it; the GenerateOutput's fields are lists with one tensor per prompt,
-    each cut to that prompt's sequence."""
+    each cut to that prompt's sequence.
+    constraint, constraint_start, logit_bias, suppress_tokens: as generate() takes them, one value or one
+    per prompt."""
     _check_logprobs(logprobs, "generate_ragged")
     prompts = list(prompts)
     if not prompts or any((not isinstance(p, torch.Tensor)) or p.dim() != 1 or p.numel() < 1 for p in prompts):
@@ -1209,15 +1453,21 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
         raise ValueError("generate_ragged: max_new_tokens must be positive")
     lens = [p.numel() for p in prompts]
     B, Smax = len(prompts), max(lens)
+    bias = _given_bias(logit_bias, suppress_tokens, B, "generate_ragged")
+    if constraint is None and constraint_start is not None:
+        raise ValueError("generate_ragged: constraint_start needs constraint")
+    slots = max((len(d) for d in bias), default=0) if bias is not None else 0
     if prompt_lookup_num_tokens is not None:
         sess = _speculative_session(model, B, Smax + max_new_tokens, prompt_lookup_num_tokens,
                                     max_matching_ngram_size, do_sample, graph, "generate_ragged",
-                                    prompt_lookup_sampling, prefill_chunk, kv_pages, kv_dtype, logprobs)
+                                    prompt_lookup_sampling, prefill_chunk, kv_pages, kv_dtype, logprobs, constraint, slots)
     elif max_matching_ngram_size is not None:
         raise ValueError("generate_ragged: max_matching_ngram_size needs prompt_lookup_num_tokens")
     else:
         sess = StreamSession(model, B, Smax + max_new_tokens, graph=graph, prefill_chunk=prefill_chunk,
-                             kv_pages=kv_pages, kv_dtype=kv_dtype, logprobs=logprobs)
+                             kv_pages=kv_pages, kv_dtype=kv_dtype, logprobs=logprobs, constraint=constraint,
+                             logit_bias_slots=slots)
+    _open_constraints(sess, bias)
     if do_sample:
         sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)
         sess.seed(generator)
@@ -1228,7 +1478,7 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     ids = torch.zeros((B, Smax), dtype=torch.int64, device=sess.device)
     for b, p in enumerate(prompts):
         ids[b, :lens[b]] = p.to(sess.device)
-    sess.prefill(ids, lens, stop=eos_token_id, max_new_tokens=max_new_tokens)
+    sess.prefill(ids, lens, stop=eos_token_id, max_new_tokens=max_new_tokens, constraint_start=constraint_start)
     if isinstance(sess, SpeculativeSession):
         _run_speculative(sess, max_new_tokens)
         return _ragged_output(sess)

@@ -1351,6 +1351,206 @@ def logprobs_streams(logits: torch.Tensor, seq: torch.Tensor, pos0: torch.Tensor
         "qz_logprobs_streams")
 
 
+def constrain_logits_supported(logits: torch.Tensor) -> bool:
+    """What qz_constrain_logits takes: fp16 / bf16 logits [R, V] on the GPU with unit element stride and
+    a row stride of at least V, at most 65535 rows.  Metadata only."""
+    return process_logits_supported(logits)
+
+
+def _check_tables(name, tables, dev):
+    if (not isinstance(tables, (tuple, list)) or len(tables) != 3
+            or not all(isinstance(t, torch.Tensor) and t.device == dev and t.is_contiguous() for t in tables)):
+        raise ValueError(f"{name}: automaton must be TokenAutomaton.to(device)'s (class_of, next, allow) on the "
+                         "operands' device")
+    class_of, nxt, allow = tables
+    if (class_of.dtype != torch.int16 or class_of.dim() != 1 or nxt.dtype != torch.int32 or nxt.dim() != 2
+            or allow.dtype != torch.int32 or allow.shape != (nxt.shape[0], (nxt.shape[1] + 31) // 32)
+            or nxt.shape[0] < 1 or not 1 <= nxt.shape[1] <= 32767):
+        raise ValueError(f"{name}: class_of int16 [V], next int32 [S, C <= 32767], allow int32 [S, ceil(C/32)]")
+    return class_of, nxt, allow
+
+
+def _constrain_logits_composed(logits, B, T, state, tok, tables, mask, bias_ids, bias_vals, bias_n) -> None:
+    """qz_constrain_logits' rules with the bookkeeping on the host (one read of the states, the drafts,
+    the tables and the lists) and the arithmetic in torch ops on the logits' device."""
+    V = logits.shape[1]
+    dev = logits.device
+    ninf = float("-inf")
+    idx = torch.arange(V, device=dev)
+    if tables is not None:
+        class_of, nxt = tables[0].cpu().long(), tables[1].cpu()
+        S, C = nxt.shape
+        states = state.cpu().tolist()
+        drafts = tok.cpu().reshape(B, T).tolist() if tok is not None else None
+    if bias_ids is not None:
+        counts = bias_n.cpu().tolist()
+    for b in range(B):
+        s = -1
+        if tables is not None:
+            s = states[b] if 0 <= states[b] < S else -1
+        for i in range(T):
+            row = logits[b * T + i]
+            if i and s >= 0:
+                d = drafts[b][i]
+                s = int(nxt[s, class_of[d]]) if 0 <= d < V else -1
+                s = s if 0 <= s < S else -1
+            if bias_ids is not None:
+                n = min(max(counts[b], 0), bias_ids.shape[1])
+                ids, vals = bias_ids[b, :n].long(), bias_vals[b, :n]
+                keep = (ids >= 0) & (ids < V) & ~torch.isnan(vals)
+                ids, vals = ids[keep], vals[keep]
+                if len(set(ids.tolist())) != ids.numel():
+                    raise ValueError("constrain_logits: the bias ids of a stream must be distinct")
+                if bool((vals == float("inf")).any()):
+                    raise ValueError("constrain_logits: a bias of +inf")
+                old = row[ids]
+                x = old.float()
+                y = torch.where(vals == ninf, vals, x + vals).to(row.dtype)
+                row[ids] = torch.where(torch.isnan(x), old, y)      # a NaN logit keeps its bits
+            if s >= 0:
+                row[(nxt[s][class_of] < 0).to(dev)] = ninf
+            if mask is not None:
+                words = mask[b, :(V + 31) // 32]
+                row[((words[idx >> 5] >> (idx & 31)) & 1) == 0] = ninf
+
+
+def constrain_logits(logits: torch.Tensor, *, state: Optional[torch.Tensor] = None,
+                     tok: Optional[torch.Tensor] = None, automaton=None, mask: Optional[torch.Tensor] = None,
+                     bias_ids: Optional[torch.Tensor] = None, bias_vals: Optional[torch.Tensor] = None,
+                     bias_n: Optional[torch.Tensor] = None, T: int = 1, composed: bool = False) -> None:
+    """Constrained decoding's masks and bias, in place, in front of a pick and behind process_logits
+    (qz_constrain_logits; include/quantizations.h states the rules).  logits [B*T, V].  Three operands,
+    each None = off:
+    state int32 [B] with automaton = TokenAutomaton.to(device)'s (class_of, next, allow): row (b, i) is
+    masked by the state reached from state[b] over the drafts tok[b, 1..i] (tok int64 [B, T], needed
+    when T > 1); every token the state refuses becomes -inf; a row whose state is negative (-1:
+    unconstrained; a refused draft in front of it) is left as it is.
+    mask int32 [B, >= ceil(V/32)] (unit element stride; xgrammar's layout, set bit = allowed; T = 1).
+    bias_ids int32 / bias_vals float32 [B, NB], bias_n int32 [B]: x' = round(float32(x) + bias) for the
+    stream's first bias_n[b] entries on all its T rows; -inf bans; ids distinct within a row.
+    The bias goes first, a mask's -inf wins.  Every value is read on the device, so a captured call
+    follows in-place changes.  fp32 or CPU logits (constrain_logits_supported is false), or
+    composed=True, take the same rules with the bookkeeping on the host (not capturable)."""
+    name = "constrain_logits"
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.stride(-1) != 1:
+        raise ValueError(f"{name}: logits must be [B*T, V] with unit element stride")
+    dev = logits.device
+    R, V = logits.shape
+    if tok is not None:
+        if not isinstance(tok, torch.Tensor) or tok.dtype != torch.int64 or tok.device != dev or not tok.is_contiguous():
+            raise ValueError(f"{name}: tok must be contiguous int64 on the logits' device")
+        if tok.dim() == 2:
+            T = tok.shape[1]
+    if not 1 <= T <= VERIFY_MAX_T:
+        raise ValueError(f"{name}: T must be in 1..{VERIFY_MAX_T}")
+    if R % T:
+        raise ValueError(f"{name}: logits must be [B*T, V]")
+    B = R // T
+    if tok is not None and tok.numel() != B * T:
+        raise ValueError(f"{name}: tok must be [B, T] (or [B] when T = 1)")
+    if (state is None) != (automaton is None):
+        raise ValueError(f"{name}: state and automaton go together")
+    tables = None
+    if state is not None:
+        tables = _check_tables(name, automaton, dev)
+        if (not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.device != dev
+                or state.shape != (B,) or not state.is_contiguous()):
+            raise ValueError(f"{name}: state must be contiguous int32 [B] on the logits' device")
+        if tables[0].shape[0] != V:
+            raise ValueError(f"{name}: the automaton is over {tables[0].shape[0]} tokens, the logits over {V}")
+        if T > 1 and tok is None:
+            raise ValueError(f"{name}: a window (T > 1) needs tok")
+    if mask is not None:
+        if T != 1:
+            raise ValueError(f"{name}: a host mask describes one row per stream; T must be 1")
+        if (not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32 or mask.device != dev or mask.dim() != 2
+                or mask.shape[0] != B or mask.shape[1] < (V + 31) // 32 or (mask.shape[1] > 1 and mask.stride(1) != 1)
+                or mask.stride(0) < mask.shape[1]):
+            raise ValueError(f"{name}: mask must be int32 [B, >= ceil(V/32)] with unit element stride")
+    given = [t is not None for t in (bias_ids, bias_vals, bias_n)]
+    if any(given) and not all(given):
+        raise ValueError(f"{name}: bias_ids, bias_vals and bias_n go together")
+    if bias_ids is not None:
+        ok = (isinstance(bias_ids, torch.Tensor) and bias_ids.dtype == torch.int32 and bias_ids.dim() == 2
+              and bias_ids.shape[0] == B and isinstance(bias_vals, torch.Tensor) and bias_vals.dtype == torch.float32
+              and bias_vals.shape == bias_ids.shape and isinstance(bias_n, torch.Tensor) and bias_n.dtype == torch.int32
+              and bias_n.shape == (B,)
+              and all(t.device == dev and t.is_contiguous() for t in (bias_ids, bias_vals, bias_n)))
+        if not ok:
+            raise ValueError(f"{name}: bias_ids int32 [B, NB], bias_vals float32 [B, NB], bias_n int32 [B], contiguous "
+                             "on the logits' device")
+    if not (B and V) or (state is None and mask is None and bias_ids is None):
+        return
+    if composed or not constrain_logits_supported(logits):
+        _constrain_logits_composed(logits, B, T, state, tok if T > 1 else None, tables, mask, bias_ids, bias_vals,
+                                   bias_n)
+        return
+    class_of, nxt, allow = tables if tables is not None else (None, None, None)
+    _lib.check(_lib.lib.qz_constrain_logits(
+        logits.data_ptr(), _lib.dtype_code(logits.dtype), B, T, V, logits.stride(0), _lib.ptr(state),
+        _lib.ptr(tok) if T > 1 else 0, _lib.ptr(class_of), _lib.ptr(allow), _lib.ptr(nxt),
+        nxt.shape[0] if nxt is not None else 0, nxt.shape[1] if nxt is not None else 0, _lib.ptr(mask),
+        mask.stride(0) if mask is not None else 0, _lib.ptr(bias_ids), _lib.ptr(bias_vals), _lib.ptr(bias_n),
+        bias_ids.shape[1] if bias_ids is not None else 0, _lib.stream_of(logits)), "qz_constrain_logits")
+
+
+def constraint_advance_supported(state: torch.Tensor, seq: torch.Tensor) -> bool:
+    """What qz_constraint_advance takes: state int32 [B] and seq int64 [B, L] (unit element stride) on
+    the GPU, at most 65535 streams.  Metadata only."""
+    return (isinstance(state, torch.Tensor) and isinstance(seq, torch.Tensor) and state.is_cuda and seq.is_cuda
+            and state.dtype == torch.int32 and seq.dtype == torch.int64 and state.shape[0] <= 65535)
+
+
+def constraint_advance(state: torch.Tensor, seq: torch.Tensor, pos0: torch.Tensor, pos1: torch.Tensor, automaton, *,
+                       composed: bool = False) -> None:
+    """Behind a pick: advance every stream's automaton state over the tokens the pick emitted
+    (qz_constraint_advance).  state int32 [B]; seq int64 [B, L] (unit element stride) is the sequence
+    itself; pos0 / pos1 int64 [1] (one position for all) or [B] are the streams' positions before and
+    after the pick; automaton = TokenAutomaton.to(device)'s tensors.  For each column c = pos0[b] + 1 ..
+    pos1[b]: state[b] = next[state[b], class_of[seq[b, c]]].  A stream that emitted nothing keeps its
+    state, a negative state stays, a refused transition or a token outside the vocabulary writes -2.
+    CPU operands, or composed=True, take the same rules on the host (not capturable)."""
+    name = "constraint_advance"
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 1 or not state.is_contiguous():
+        raise ValueError(f"{name}: state must be contiguous int32 [B]")
+    dev = state.device
+    B = state.shape[0]
+    if (not isinstance(seq, torch.Tensor) or seq.dtype != torch.int64 or seq.device != dev or seq.dim() != 2
+            or seq.shape[0] != B or (seq.shape[1] > 1 and seq.stride(1) != 1) or seq.stride(0) < seq.shape[1]):
+        raise ValueError(f"{name}: seq must be int64 [B, L] with unit element stride on the state's device")
+    L = seq.shape[1]
+    for t, what in ((pos0, "pos0"), (pos1, "pos1")):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.device != dev or not t.is_contiguous()
+                or t.numel() not in (1, B)):
+            raise ValueError(f"{name}: {what} must be contiguous int64 [1] or [B] on the state's device")
+    class_of, nxt, _ = _check_tables(name, automaton, dev)
+    V, (S, C) = class_of.shape[0], nxt.shape
+    if not (B and L):
+        return
+    if composed or not constraint_advance_supported(state, seq):
+        st, rows = state.cpu().tolist(), seq.cpu().tolist()
+        p0, p1 = pos0.cpu().reshape(-1).tolist(), pos1.cpu().reshape(-1).tolist()
+        co, nx = class_of.cpu().tolist(), nxt.cpu()
+        for b in range(B):
+            lo, hi = max(p0[b if len(p0) > 1 else 0] + 1, 0), min(p1[b if len(p1) > 1 else 0], L - 1)
+            s = st[b]
+            if lo > hi or s < 0:
+                continue
+            s = s if s < S else -1
+            for c in range(lo, hi + 1):
+                t = rows[b][c]
+                s = int(nx[s, co[t]]) if (s >= 0 and 0 <= t < V) else -1
+                if not 0 <= s < S:
+                    s = -1
+                    break
+            state[b] = s if s >= 0 else -2
+        return
+    _lib.check(_lib.lib.qz_constraint_advance(
+        state.data_ptr(), B, seq.data_ptr(), seq.stride(0), L, pos0.data_ptr(), 0 if pos0.numel() == 1 and B > 1 else 1,
+        pos1.data_ptr(), 0 if pos1.numel() == 1 and B > 1 else 1, class_of.data_ptr(), nxt.data_ptr(), V, S, C,
+        _lib.stream_of(state)), "qz_constraint_advance")
+
+
 def ngram_draft_reference(seq, tok0: int, p: int, T: int, ngram_max: int) -> list:
     """The drafter's rule on host integers: seq[0..p] is the stream's history (seq[p] the newest
     token), the result its T - 1 drafts."""

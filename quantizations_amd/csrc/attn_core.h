@@ -24,13 +24,6 @@ namespace qz {
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kAttnChunk = 128;  // key positions per workgroup
-// QZ_ATTN_ABL (measurement builds only, scripts/dev/attn_ablation.py; 0 in the product): drop one
-// phase to price it -- 1 the arrival atomic, 2 the cache row loads, 4 P V, 8 the scores,
-// 16 the softmax exponentials, 32 everything after the loads
-#ifndef QZ_ATTN_ABL
-#define QZ_ATTN_ABL 0
-#endif
-constexpr int kAttnAbl = QZ_ATTN_ABL;
 constexpr int kAttnMaxG = 8;     // query heads per kv head
 constexpr int kAttnSpecL = 512;  // caches read before their mask arrives (speculatively) up to this length
 
@@ -208,35 +201,86 @@ __device__ __forceinline__ void kv_write_row(const Args &a, long long r, int h, 
   }
 }
 
+// Diagnostic timeline stamps of the decode head (measurement-only builds: diag_stamps.hip defines
+// QZ_STAMPS and passes a stamp buffer; the product library compiles none of this).  Per wave,
+// s_memrealtime (100 MHz, chip-wide) at: 0 entry, 1 every load issued, 2 the wave's K half rows in
+// registers, 3 the first workgroup barrier passed, 4 the V half rows in registers, 5 P V done, 6 the
+// output store issued; lane 0 stores them at the end, 8 u64 per wave.  QZ_ATTN_ARRIVED pins the
+// arrival of a load array in front of a stamp (an empty asm that uses every register of it).
+#ifdef QZ_STAMPS
+#define QZ_ATTN_STAMP_DECL unsigned long long qz_at_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+#define QZ_ATTN_STAMP(k)                                                                 \
+  do {                                                                                   \
+    __builtin_amdgcn_sched_barrier(0);                                                   \
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(qz_at_[k])::"memory"); \
+    __builtin_amdgcn_sched_barrier(0);                                                   \
+  } while (0)
+#define QZ_ATTN_ARRIVED(arr, n)                                   \
+  do {                                                            \
+    _Pragma("unroll") for (int i_ = 0; i_ < (n); ++i_) asm volatile("" : "+v"((arr)[i_])); \
+  } while (0)
+#define QZ_ATTN_STAMP_FLUSH(buf, wave_id)                                                   \
+  do {                                                                                      \
+    if ((buf) != nullptr && (threadIdx.x & 63) == 0) {                                      \
+      for (int k_ = 0; k_ < 8; ++k_) (buf)[(size_t)(wave_id) * 8 + k_] = qz_at_[k_];        \
+    }                                                                                       \
+  } while (0)
+#else
+#define QZ_ATTN_STAMP_DECL
+#define QZ_ATTN_STAMP(k) do {} while (0)
+#define QZ_ATTN_ARRIVED(arr, n) do {} while (0)
+#define QZ_ATTN_STAMP_FLUSH(buf, wave_id) do {} while (0)
+#endif
+
+// A DPP move of an fp32 (every lane of the wave active): CTRL 0x120 + n is row_ror:n, a rotation inside
+// each row of 16 lanes; 0xB1 is quad_perm:[1,0,3,2], lane l <- lane l ^ 1.
+template <int CTRL> __device__ __forceinline__ float dpp_f32(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
+}
+// f over the 16 lanes of each row, left in every lane of the row: rotations by 8, 4, 2, 1.  After the
+// step by n the value is the same in lanes that differ in bits >= n only, so the lane a rotation
+// reaches holds what lane l ^ n holds: the xor butterfly's pairs, in its order.
+template <class F> __device__ __forceinline__ float row16_butterfly(float v, F &&f) {
+  v = f(v, dpp_f32<0x128>(v));
+  v = f(v, dpp_f32<0x124>(v));
+  v = f(v, dpp_f32<0x122>(v));
+  v = f(v, dpp_f32<0x121>(v));
+  return v;
+}
+// a workgroup barrier that waits for this wave's LDS accesses only: global loads issued before it stay
+// in flight across it (its vmcnt is not touched)
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
 // LDS of one head's attention.  `v` is the staged v rows, kAttnChunk x H2 words with the word
-// columns XOR-swizzled by (position & 31): a thread writes its half row at one column across 32
+// columns XOR-swizzled by (position & 31): a lane writes its half row at one column across 32
 // consecutive positions per instruction, so an unswizzled 64-word row put every lane of a write
 // group on one bank (profiles/r5_attn_vpad_ab.txt: 6.80 -> 6.43 us per launch with the rows
-// spread); the P V reads (one row, consecutive columns) stay conflict-free.  The rest is small.
+// spread); the P V reads (one row, consecutive columns) stay conflict-free.  Wave w stages and reads
+// rows [32 w, 32 w + 32) only.  The rest is small; qh, p, kn and vn are wave-private too.
 template <int D> struct AttnLds {
   static constexpr int H2 = D / 2;
   static constexpr int NSUB = kWave / H2;
   static constexpr int kVBytes = kAttnChunk * H2 * 4;
   // small-region offsets (bytes, 16-B aligned)
-  static constexpr int oQh = 0;                               // rotated q, raw [H2 words]
-  static constexpr int oSc = oQh + H2 * 4;                    // half-row partial scores [2][kAttnChunk]
-  static constexpr int oP = oSc + 2 * kAttnChunk * 4;         // probabilities [kAttnChunk]
+  static constexpr int oQh = 0;                               // rotated q, raw, one copy per wave [4][H2 words]
+  static constexpr int oMx = oQh + 4 * H2 * 4;                // the waves' score maxima [4]
+  static constexpr int oU = oMx + 16;                         // the waves' pair sums of e [4][16]
+  static constexpr int oP = oU + 4 * 16 * 4;                  // probabilities [kAttnChunk]
   static constexpr int oKn = oP + kAttnChunk * 4;             // the new rotated k, raw [H2]
   static constexpr int oVn = oKn + H2 * 4;                    // the new v, raw [H2]
-  static constexpr int oOk = oVn + H2 * 4;                    // mask bytes [kAttnChunk]
-  static constexpr int oPv = oOk + kAttnChunk;                // P V partials [4 NSUB][D]
-  static constexpr int oMl = oPv + 4 * NSUB * D * 4;          // max, sum
-  static constexpr int kSmallBytes = oMl + 16;
+  static constexpr int oPv = oVn + H2 * 4;                    // P V partials [4 NSUB][D]
+  static constexpr int kSmallBytes = oPv + 4 * NSUB * D * 4;
   uint32_t *v;
   unsigned char *small;
   __device__ uint32_t *qh() const { return reinterpret_cast<uint32_t *>(small + oQh); }
-  __device__ float *sc() const { return reinterpret_cast<float *>(small + oSc); }
+  __device__ float *mx() const { return reinterpret_cast<float *>(small + oMx); }
+  __device__ float *u() const { return reinterpret_cast<float *>(small + oU); }
   __device__ float *p() const { return reinterpret_cast<float *>(small + oP); }
   __device__ uint32_t *kn() const { return reinterpret_cast<uint32_t *>(small + oKn); }
   __device__ uint32_t *vn() const { return reinterpret_cast<uint32_t *>(small + oVn); }
-  __device__ unsigned char *ok() const { return small + oOk; }
   __device__ float *pv() const { return reinterpret_cast<float *>(small + oPv); }
-  __device__ float *ml() const { return reinterpret_cast<float *>(small + oMl); }
   __device__ uint32_t &vw(int pos, int col) const { return v[pos * H2 + (col ^ (pos & 31))]; }
 };
 
@@ -258,10 +302,26 @@ template <int D> struct AttnLds {
 // scale bytes and converts them to packed 16-bit pairs where the 16-bit form unpacks its loads; the new
 // token's rows are quantised, stored and DEQUANTISED before they go to s_kn / s_vn, so the step
 // scores what every later step reads back.  Everything from kw[] / vw[] on is the same code.
-template <int DT, int D, bool STREAMS = false, bool VERIFY = false, bool PAGED = false, bool KV8 = false>
-__device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, int split, int hq, int b,
-                                                      const AttnLds<D> &S, int cb = 0, long long pv = 0,
-                                                      int page = 0) {
+//
+// Schedule.  Wave w owns positions j0 + 32 w .. + 31: lane l takes position 32 w + (l & 31), row half
+// l >> 5.  Everything between the loads and the final sum stays inside a wave except two small
+// exchanges -- the four score maxima (barrier A) and the waves' pair sums of e (barrier B) -- and both
+// barriers wait for LDS only, so they are passed while the V rows are still in flight: the softmax
+// needs K alone.  A wave stages the V rows it consumes itself (no workgroup barrier between staging
+// and P V); the only barrier behind the V arrival is the one in front of the final sum.
+// The arithmetic is that of the one-wave softmax this replaces, operation for operation: the half-row
+// scores are the same two dot2 chains and meet in the same fp32 add; fmaxf is order-free; the sum of
+// e keeps the tree "leaves e[2i] + e[2i+1], then the xor butterfly over i with offsets 32, 16, 8, 4,
+// 2, 1" (offsets 32 and 16 are the waves' exchange, the rest row16_butterfly); P V and the final sum
+// are unchanged.
+// SPEC: the cache is at most kAttnSpecL long and its rows are read before their mask.  The early loads
+// are branch-free -- a lane past L reads row j0, a lane that rotates nothing reads a pair another
+// lane reads -- because hipcc counts a wait (vmcnt(N), loads behind it left in flight) only while no
+// branch stands between a load and its wait; behind a branch it drains every load (vmcnt(0)).
+template <int DT, int D, bool STREAMS, bool VERIFY, bool PAGED, bool KV8, bool SPEC>
+__device__ __forceinline__ long long decode_attn_body(const DecodeAttnArgs &a, int split, int hq, int b,
+                                                      const AttnLds<D> &S, int cb, long long pv, int page,
+                                                      unsigned long long *stamps) {
   static_assert(STREAMS || !VERIFY, "the verify form computes its mask from the position");
   static_assert(STREAMS || !PAGED, "the paged form has a position per stream");
   static_assert(PAGED || !KV8, "kv8 rows live in page pools");
@@ -270,61 +330,73 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
   constexpr int H2 = D / 2;      // rotary half; also the share of a row one thread dots
   constexpr int NW = H2 / 2;     // 32-bit words of half a row
   constexpr int NSUB = kWave / H2;  // P V: lane groups per wave (D = 128: 1, D = 64: 2)
-  uint32_t *s_qh = S.qh(), *s_kn = S.kn(), *s_vn = S.vn();
-  float *s_p = S.p(), *s_pv = S.pv(), *s_ml = S.ml();
-  float *s_sc = S.sc();
-  unsigned char *s_ok = S.ok();
+  QZ_ATTN_STAMP_DECL;
+  QZ_ATTN_STAMP(0);
+  // p first: a uniform load in front of every asm statement stays a scalar load
+  const long long p = VERIFY ? pv : STREAMS ? a.pos[b] : *a.pos;
+  // the arguments the tail needs, read once and kept in SGPRs
+  const float scale = keep_s(a.scale);
+  void *const out = keep_sp(a.out);
+  float *const part = keep_sp(a.part);
+  const long long os = keep_s(a.os);
+  const int nsplit = keep_s(a.nsplit), G = keep_s(a.G), L = keep_s(a.L), Hkv = keep_s(a.Hkv);
 
   const int t = threadIdx.x;
-  const int G = a.G, L = a.L;
+  const int w = __builtin_amdgcn_readfirstlane(t / kWave), lane = t & (kWave - 1);
+  uint32_t *s_qh = S.qh() + w * H2, *s_kn = S.kn(), *s_vn = S.vn();
+  float *s_p = S.p(), *s_pv = S.pv(), *s_mx = S.mx(), *s_u = S.u();
   const int h = hq / G, gq = hq - h * G;                     // kv head, query head within it
   const int j0 = split * kAttnChunk;
-  const long long crow = PAGED ? ((long long)page * a.Hkv + h) * kAttnChunk - j0   // row of key 0, were the pages in line
-                               : ((long long)(VERIFY ? cb : b) * a.Hkv + h) * L;  // first cache row of (b, h)
-  const int pos_i = t & (kAttnChunk - 1), half = t >> 7;     // this thread's key position / row half
+  const long long crow = PAGED ? ((long long)page * Hkv + h) * kAttnChunk - j0   // row of key 0, were the pages in line
+                               : ((long long)(VERIFY ? cb : b) * Hkv + h) * L;   // first cache row of (b, h)
+  const int pos_i = 32 * w + (lane & 31), half = lane >> 5;  // this thread's key position / row half
   const long long j = j0 + pos_i;
   const bool in_l = j < L;
 
   // 0. Every global load goes out before anything waits (a decode step's attention is bound by
   //    latency, not bandwidth): p, the q / cos / sin / new k and v operands of the rotary
-  //    (threads below H2: one pair each), then the mask byte and the half rows of k and v at
-  //    position j -- whatever the mask says (a masked row is dropped after it arrives) -- for
-  //    caches up to kAttnSpecL positions; a longer cache is read after its mask, so a long
+  //    (lanes below H2 of every wave: one pair each), then the mask byte and the half rows of k
+  //    and v at position j -- whatever the mask says (a masked row is dropped after it arrives) --
+  //    for caches up to kAttnSpecL positions; a longer cache is read after its mask, so a long
   //    static cache early in a sequence does not stream its masked rows.
-  const long long p = VERIFY ? pv : STREAMS ? a.pos[b] : *a.pos;
-  const bool rt = t < H2;
-  float x1 = 0.f, x2 = 0.f, c1 = 0.f, c2 = 0.f, s1 = 0.f, s2 = 0.f, k1 = 0.f, k2 = 0.f;
+  const bool rt = lane < H2;
+  const int ri = lane & (H2 - 1);             // the lane's rotary pair (a lane past H2 reads a pair again and drops it)
+  uint16_t x1b, x2b, c1b, c2b, s1b, s2b, k1b = 0, k2b = 0;   // raw: converted behind the loads
   uint32_t vnew = 0u;
-  if (rt) {
+  {
     const char *cb = reinterpret_cast<const char *>(a.cos) + (long long)b * a.cs * ES;
     const char *sb = reinterpret_cast<const char *>(a.sin) + (long long)b * a.cs * ES;
     const char *qb = reinterpret_cast<const char *>(a.q) + ((long long)b * a.qs + (long long)hq * D) * ES;
     const char *kb = reinterpret_cast<const char *>(a.k) + ((long long)b * a.ks + (long long)h * D) * ES;
     const char *vb = reinterpret_cast<const char *>(a.v) + ((long long)b * a.vs + (long long)h * D) * ES;
-    x1 = load_f32<DT>(qb, t); x2 = load_f32<DT>(qb, t + H2);
+    auto raw = [](const char *base, int i) { return reinterpret_cast<const uint16_t *>(base)[i]; };
+    x1b = raw(qb, ri); x2b = raw(qb, ri + H2);
     if constexpr (!VERIFY) {
-      k1 = load_f32<DT>(kb, t); k2 = load_f32<DT>(kb, t + H2);
-      vnew = reinterpret_cast<const uint32_t *>(vb)[t];  // elements 2t, 2t + 1
+      k1b = raw(kb, ri); k2b = raw(kb, ri + H2);
+      vnew = reinterpret_cast<const uint32_t *>(vb)[ri];  // elements 2 ri, 2 ri + 1
     }
-    c1 = load_f32<DT>(cb, t); c2 = load_f32<DT>(cb, t + H2);
-    s1 = load_f32<DT>(sb, t); s2 = load_f32<DT>(sb, t + H2);
+    c1b = raw(cb, ri); c2b = raw(cb, ri + H2);
+    s1b = raw(sb, ri); s2b = raw(sb, ri + H2);
   }
   unsigned char mk;
   if constexpr (STREAMS) mk = (in_l && j <= p) ? (unsigned char)1 : (unsigned char)0;
-  else mk = in_l ? a.mask[(long long)b * a.mb + j * a.mj] : (unsigned char)0;
+  else mk = a.mask[(long long)b * a.mb + (in_l ? j : 0) * a.mj];   // past L: key 0's byte, dropped below
   constexpr int NR = KV8 ? NW / 8 : NW / 4;   // 16-B loads of half a row
   u32x4 kr[NR], vr[NR];
   uint32_t ksb = 127u, vsb = 127u;            // KV8: the rows' scale bytes
-  const bool spec = L <= kAttnSpecL;
-  const long long blk8 = KV8 ? ((long long)page * a.Hkv + h) * Kv8<D>::kBlock : 0;   // KV8: this (page, kv head)
+  const long long blk8 = KV8 ? ((long long)page * Hkv + h) * Kv8<D>::kBlock : 0;   // KV8: this (page, kv head)
   const long long roff = KV8 ? blk8 + pos_i * D + half * H2 : ((crow + j) * D + half * H2) * ES;
   const u32x4 *kp = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(a.kc) + roff);
   const u32x4 *vp = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(a.vc) + roff);
-  if (in_l && spec && (kAttnAbl & 2) == 0) {
+  if constexpr (SPEC) {
+    // past L (the 16-bit contiguous form only: a page is whole): the chunk's first row, dropped below
+    const long long back = KV8 || in_l ? 0 : (long long)pos_i * D * ES;
+    const u32x4 *kq = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(kp) - back);
+    const u32x4 *vq = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(vp) - back);
 #pragma unroll
-    for (int i = 0; i < NR; ++i) kr[i] = kp[i];
+    for (int i = 0; i < NR; ++i) kr[i] = kq[i];
 #pragma unroll
-    for (int i = 0; i < NR; ++i) vr[i] = vp[i];
+    for (int i = 0; i < NR; ++i) vr[i] = vq[i];
     if constexpr (KV8) {
       ksb = reinterpret_cast<const unsigned char *>(a.kc)[blk8 + Kv8<D>::kScales + pos_i];
       vsb = reinterpret_cast<const unsigned char *>(a.vc)[blk8 + Kv8<D>::kScales + pos_i];
@@ -334,150 +406,179 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
     for (int i = 0; i < NR; ++i) kr[i] = vr[i] = u32x4{0u, 0u, 0u, 0u};
   }
   __builtin_amdgcn_sched_barrier(0);
+  QZ_ATTN_STAMP(1);
+  const float x1 = from_bits<DT>(x1b), x2 = from_bits<DT>(x2b), c1 = from_bits<DT>(c1b), c2 = from_bits<DT>(c2b);
+  const float s1 = from_bits<DT>(s1b), s2 = from_bits<DT>(s2b), k1 = from_bits<DT>(k1b), k2 = from_bits<DT>(k2b);
 
-  // 1. rotary of this query head (and, in the chunk holding p, of the new key), k_rope_qk's
-  //    arithmetic: q*cos + cat(-x2, x1)*sin with every torch op rounded to the storage dtype.  The
-  //    G query heads of one kv head all rotate the new key (bit-identical values); the first of
-  //    them writes the cache rows.
+  // 1. rotary of this query head, by every wave for itself (bit-identical copies in s_qh[w]), and, in
+  //    the wave that owns position p, of the new key: k_rope_qk's arithmetic, q*cos + cat(-x2, x1)*sin
+  //    with every torch op rounded to the storage dtype.  The G query heads of one kv head all rotate
+  //    the new key (bit-identical values); the first of them writes the cache rows.  No workgroup
+  //    barrier follows: s_qh[w], s_kn and s_vn are read by the wave that wrote them.
   auto rope = [&](float u1, float u2, float &lo, float &hi) {
     lo = from_bits<DT>(bits_dt<DT>(__fadd_rn(round_dt<DT>(__fmul_rn(u1, c1)), round_dt<DT>(__fmul_rn(-u2, s1)))));
     hi = from_bits<DT>(bits_dt<DT>(__fadd_rn(round_dt<DT>(__fmul_rn(u2, c2)), round_dt<DT>(__fmul_rn(u1, s2)))));
   };
   const bool mine = !VERIFY && p >= j0 && p < j0 + kAttnChunk && p < L;  // this chunk holds the new token
+  const bool own = mine && w == (int)((p - j0) >> 5);                     // and this wave its position
+  float klo = 0.0f, khi = 0.0f;   // the new key's pair, kept for the cache row store at the end
   if (rt) {
     float lo, hi;
     rope(x1, x2, lo, hi);
-    reinterpret_cast<uint16_t *>(s_qh)[t] = (uint16_t)bits_dt<DT>(lo);
-    reinterpret_cast<uint16_t *>(s_qh)[t + H2] = (uint16_t)bits_dt<DT>(hi);
-    if (mine) {
+    reinterpret_cast<uint16_t *>(s_qh)[lane] = (uint16_t)bits_dt<DT>(lo);
+    reinterpret_cast<uint16_t *>(s_qh)[lane + H2] = (uint16_t)bits_dt<DT>(hi);
+    if (own) {
       rope(k1, k2, lo, hi);
       if constexpr (KV8) {
-        kv8_put_row<DT, D>(lo, hi, vnew, t, gq == 0, reinterpret_cast<unsigned char *>(a.kc) + blk8,
+        kv8_put_row<DT, D>(lo, hi, vnew, lane, gq == 0, reinterpret_cast<unsigned char *>(a.kc) + blk8,
                            reinterpret_cast<unsigned char *>(a.vc) + blk8, (int)(p & (kAttnChunk - 1)));
-      } else if (gq == 0) {
-        char *kd = reinterpret_cast<char *>(a.kc) + (crow + p) * D * ES;
-        char *vd = reinterpret_cast<char *>(a.vc) + (crow + p) * D * ES;
-        store_f32<DT>(kd, t, lo);
-        store_f32<DT>(kd, t + H2, hi);
-        reinterpret_cast<uint32_t *>(vd)[t] = vnew;
       }
-      s_vn[t] = vnew;
+      klo = lo; khi = hi;
+      s_vn[lane] = vnew;
       // the rotated k as raw elements: element e in the 16-bit half e % 2 of s_kn[e / 2]
-      reinterpret_cast<uint16_t *>(s_kn)[t] = (uint16_t)bits_dt<DT>(lo);
-      reinterpret_cast<uint16_t *>(s_kn)[t + H2] = (uint16_t)bits_dt<DT>(hi);
+      reinterpret_cast<uint16_t *>(s_kn)[lane] = (uint16_t)bits_dt<DT>(lo);
+      reinterpret_cast<uint16_t *>(s_kn)[lane + H2] = (uint16_t)bits_dt<DT>(hi);
     }
   }
-  __syncthreads();
-  if constexpr ((kAttnAbl & 32) != 0) {
-    if (t < 2 * H2) { float acc = 0.f;
-#pragma unroll
-      for (int i = 0; i < NW / 4; ++i) acc += __uint_as_float(kr[i].x ^ vr[i].y);
-      reinterpret_cast<float *>(a.out)[t] = acc + __uint_as_float(s_qh[t & (H2 - 1)]); }
-    return p;
-  }
+  // the wave's own LDS writes, in front of its own reads
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-  // 2. half-row dot products: thread t scores position t % 128 over dims [H2 * (t / 128), + H2)
-  //    and stages that half of the position's v row in LDS (zeros where masked / past L)
-  {
-    const bool ok = mk != 0;
-    if (!spec && ok && (VERIFY || j != p)) {  // long cache: the rows the mask keeps, read now
+  // 2. half-row dot products: lane l scores position 32 w + l % 32 over dims [H2 * (l / 32), + H2);
+  //    the two halves of a position meet in the wave (lanes l, l ^ 32)
+  const bool ok = in_l && mk != 0;
+  const bool is_new = !VERIFY && ok && j == p;
+  if (!SPEC && ok && (VERIFY || j != p)) {  // long cache: the rows the mask keeps, read now
 #pragma unroll
-      for (int i = 0; i < NR; ++i) kr[i] = kp[i];
+    for (int i = 0; i < NR; ++i) kr[i] = kp[i];
 #pragma unroll
-      for (int i = 0; i < NR; ++i) vr[i] = vp[i];
-      if constexpr (KV8) {
-        ksb = reinterpret_cast<const unsigned char *>(a.kc)[blk8 + Kv8<D>::kScales + pos_i];
-        vsb = reinterpret_cast<const unsigned char *>(a.vc)[blk8 + Kv8<D>::kScales + pos_i];
-      }
+    for (int i = 0; i < NR; ++i) vr[i] = vp[i];
+    if constexpr (KV8) {
+      ksb = reinterpret_cast<const unsigned char *>(a.kc)[blk8 + Kv8<D>::kScales + pos_i];
+      vsb = reinterpret_cast<const unsigned char *>(a.vc)[blk8 + Kv8<D>::kScales + pos_i];
     }
-    uint32_t kw[NW], vw[NW];
-    if (!VERIFY && ok && j == p) {
+  }
+  float sc;
+  {
+    QZ_ATTN_ARRIVED(kr, NR);
+    QZ_ATTN_STAMP(2);
+    uint32_t kw[NW];
+    if (is_new) {
 #pragma unroll
-      for (int i = 0; i < NW; ++i) { kw[i] = s_kn[half * NW + i]; vw[i] = s_vn[half * NW + i]; }
+      for (int i = 0; i < NW; ++i) kw[i] = s_kn[half * NW + i];
     } else if constexpr (KV8) {
 #pragma unroll
-      for (int i = 0; i < NR; ++i) {
-        kv8_dq16<DT>(kr[i], ksb, &kw[8 * i]);
-        kv8_dq16<DT>(vr[i], vsb, &vw[8 * i]);
-      }
+      for (int i = 0; i < NR; ++i) kv8_dq16<DT>(kr[i], ksb, &kw[8 * i]);
       if (!ok) {
 #pragma unroll
-        for (int i = 0; i < NW; ++i) kw[i] = vw[i] = 0u;
+        for (int i = 0; i < NW; ++i) kw[i] = 0u;
       }
     } else {
 #pragma unroll
       for (int i = 0; i < NW / 4; ++i) {
         kw[4 * i] = kr[i].x; kw[4 * i + 1] = kr[i].y; kw[4 * i + 2] = kr[i].z; kw[4 * i + 3] = kr[i].w;
+      }
+      if (!ok) {
+#pragma unroll
+        for (int i = 0; i < NW; ++i) kw[i] = 0u;
+      }
+    }
+    // both operands are storage-dtype values: v_dot2 of the raw pairs, products exact in fp32
+    const uint32_t *qw = &s_qh[half * NW];
+    float acc0 = 0.0f, acc1 = 0.0f;  // two chains: even / odd words
+#pragma unroll
+    for (int i = 0; i < NW; i += 2) {
+      acc0 = dot2_dt<DT>(kw[i], qw[i], acc0);
+      acc1 = dot2_dt<DT>(kw[i + 1], qw[i + 1], acc1);
+    }
+    const uint32_t hs = __float_as_uint(__fadd_rn(acc0, acc1));
+    // v_permlane32_swap of a value with itself: element 0 is the lower lanes' value in both halves of
+    // the wave, element 1 the upper lanes' -- the half-0 and the half-1 score of the lane's position
+    const auto sw = __builtin_amdgcn_permlane32_swap(hs, hs, false, false);
+    const float tot = __fadd_rn(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+    sc = ok ? __fmul_rn(tot, scale) : -INFINITY;
+  }
+
+  // 3. softmax statistics of the chunk.  The maximum: over the wave's 32 positions (both halves of the
+  //    wave hold them), the four waves' through LDS.
+  {
+    const float mr = row16_butterfly(sc, [](float x, float y) { return fmaxf(x, y); });
+    const float mw = fmaxf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(mr), 0)),
+                           __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mr), 16)));
+    if (lane == 0) s_mx[w] = mw;
+  }
+  lds_barrier();  // A
+  QZ_ATTN_STAMP(3);
+  const float m = fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
+  const float e = sc == -INFINITY ? 0.0f : expf(sc - m);
+  float l;
+  {
+    // leaves e[2i] + e[2i+1] (lanes l, l ^ 1); leaf i = 16 w + (l & 31) / 2
+    const float eo = dpp_f32<0xB1>(e);
+    const float u = (lane & 1) ? __fadd_rn(eo, e) : __fadd_rn(e, eo);
+    if ((lane & 33) == 0) s_u[16 * w + (lane >> 1)] = u;
+    if (half == 0) s_p[pos_i] = e;
+    lds_barrier();  // B
+    // offsets 32 and 16 of the butterfly over i: waves w, w ^ 2, then w, w ^ 1
+    const int i = lane & 15;
+    const float U = __fadd_rn(__fadd_rn(s_u[i], s_u[32 + i]), __fadd_rn(s_u[16 + i], s_u[48 + i]));
+    const float lr = row16_butterfly(U, [](float x, float y) { return __fadd_rn(x, y); });
+    l = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lr), 0));
+  }
+  __builtin_amdgcn_sched_barrier(0);
+
+  // 4. P V: the wave stages the v rows of its positions [32 w, 32 w + 32) (zeros where masked / past L)
+  //    and consumes them itself: lane group ps of the wave every NSUB-th of them, lane pl one output
+  //    pair; the 4 * NSUB slice partials meet in LDS
+  {
+    QZ_ATTN_ARRIVED(vr, NR);
+    QZ_ATTN_STAMP(4);
+    uint32_t vw[NW];
+    if (is_new) {
+#pragma unroll
+      for (int i = 0; i < NW; ++i) vw[i] = s_vn[half * NW + i];
+    } else if constexpr (KV8) {
+#pragma unroll
+      for (int i = 0; i < NR; ++i) kv8_dq16<DT>(vr[i], vsb, &vw[8 * i]);
+      if (!ok) {
+#pragma unroll
+        for (int i = 0; i < NW; ++i) vw[i] = 0u;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NW / 4; ++i) {
         vw[4 * i] = vr[i].x; vw[4 * i + 1] = vr[i].y; vw[4 * i + 2] = vr[i].z; vw[4 * i + 3] = vr[i].w;
       }
       if (!ok) {
 #pragma unroll
-        for (int i = 0; i < NW; ++i) kw[i] = vw[i] = 0u;
+        for (int i = 0; i < NW; ++i) vw[i] = 0u;
       }
     }
-    if (half == 0) s_ok[pos_i] = ok ? 1 : 0;
 #pragma unroll
     for (int i = 0; i < NW; ++i) S.vw(pos_i, half * NW + i) = vw[i];
-    if constexpr ((kAttnAbl & 8) == 0) {
-      // both operands are storage-dtype values: v_dot2 of the raw pairs, products exact in fp32
-      const uint32_t *qw = &s_qh[half * NW];
-      float acc0 = 0.0f, acc1 = 0.0f;  // two chains: even / odd words
-#pragma unroll
-      for (int i = 0; i < NW; i += 2) {
-        acc0 = dot2_dt<DT>(kw[i], qw[i], acc0);
-        acc1 = dot2_dt<DT>(kw[i + 1], qw[i + 1], acc1);
-      }
-      s_sc[half * kAttnChunk + pos_i] = __fadd_rn(acc0, acc1);
-    }
-  }
-  __syncthreads();
-
-  // 3. softmax statistics of the chunk: wave 0, two positions per lane
-  if (t < kWave) {
-    float s[2], m = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int pi = 2 * t + r;
-      s[r] = s_ok[pi] ? __fmul_rn(__fadd_rn(s_sc[pi], s_sc[kAttnChunk + pi]), a.scale) : -INFINITY;
-      m = fmaxf(m, s[r]);
-    }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, kWave));
-    float l = 0.0f, e[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      e[r] = s[r] == -INFINITY ? 0.0f : ((kAttnAbl & 16) ? s[r] - m : expf(s[r] - m));
-      l += e[r];
-    }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) l += __shfl_xor(l, o, kWave);
-    s_p[2 * t] = e[0];
-    s_p[2 * t + 1] = e[1];
-    if (t == 0) { s_ml[0] = m; s_ml[1] = l; }
-  }
-  __syncthreads();
-
-  // 4. P V: wave w takes positions [32 w, 32 w + 32), lane group ps of the wave every NSUB-th of
-  //    them, lane pl one output pair; the 4 * NSUB slice partials meet in LDS
-  {
-    const int w = t / kWave, lane = t & (kWave - 1), pl = lane % H2, ps = lane / H2;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int pl = lane % H2, ps = lane / H2;
     float e0 = 0.0f, e1 = 0.0f;
-    if constexpr ((kAttnAbl & 4) == 0) {
-      // a fixed trip count, fully unrolled (every LDS read issued before the FMAs wait): rows
-      // past L are zero in the v image and s_p
+    // a fixed trip count, fully unrolled (every LDS read issued before the FMAs wait): rows
+    // past L are zero in the v image and in e
 #pragma unroll
-      for (int i = 0; i < 32 / NSUB; ++i) {
-        const int q = 32 * w + ps + NSUB * i;
-        const float pr = s_p[q];
-        const uint32_t vv = S.vw(q, pl);
-        e0 = fmaf(pr, from_bits<DT>(vv), e0);
-        e1 = fmaf(pr, from_bits<DT>(vv >> 16), e1);
-      }
+    for (int i = 0; i < 32 / NSUB; ++i) {
+      const int q = 32 * w + ps + NSUB * i;
+      float pr;
+      if constexpr (NSUB == 1) pr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), i));
+      else pr = s_p[q];
+      const uint32_t vv = S.vw(q, pl);
+      e0 = fmaf(pr, from_bits<DT>(vv), e0);
+      e1 = fmaf(pr, from_bits<DT>(vv >> 16), e1);
     }
     s_pv[(w * NSUB + ps) * D + 2 * pl] = e0;
     s_pv[(w * NSUB + ps) * D + 2 * pl + 1] = e1;
   }
-  __syncthreads();
+  QZ_ATTN_STAMP(5);
+  __syncthreads();  // C
   if (t < D) {
     float acc = 0.0f;
 #pragma unroll
@@ -485,16 +586,38 @@ __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, i
     // a full cache (p >= L) has no slot for the new token: HF's StaticLayer.update fails on the
     // out-of-range index_copy_; here the output is NaN (never a silently stale attention)
     if (p >= L) acc = __builtin_nanf("");
-    if (a.nsplit == 1) {
-      char *ob = reinterpret_cast<char *>(a.out) + ((long long)b * a.os + (long long)hq * D) * ES;
-      store_f32<DT>(ob, t, __fdiv_rn(acc, s_ml[1]));
+    if (nsplit == 1) {
+      char *ob = reinterpret_cast<char *>(out) + ((long long)b * os + (long long)hq * D) * ES;
+      store_f32<DT>(ob, t, __fdiv_rn(acc, l));
     } else {
-      float *pp = a.part + ((((long long)b * a.Hkv + h) * a.nsplit + split) * G + gq) * (D + 2);
+      float *pp = part + ((((long long)b * Hkv + h) * nsplit + split) * G + gq) * (D + 2);
       pp[t] = acc;
-      if (t == 0) { pp[D] = s_ml[0]; pp[D + 1] = s_ml[1]; }
+      if (t == 0) { pp[D] = m; pp[D + 1] = l; }
     }
   }
+  QZ_ATTN_STAMP(6);
+  // the new token's cache rows, by the wave that rotated them in the kv head's first workgroup: last, so
+  // that no wait above counts these stores (nothing in this launch reads them back)
+  if constexpr (!KV8) {
+    if (rt && own && gq == 0) {
+      char *kd = reinterpret_cast<char *>(a.kc) + (crow + p) * D * ES;
+      char *vd = reinterpret_cast<char *>(a.vc) + (crow + p) * D * ES;
+      store_f32<DT>(kd, lane, klo);
+      store_f32<DT>(kd, lane + H2, khi);
+      reinterpret_cast<uint32_t *>(vd)[lane] = vnew;
+    }
+  }
+  QZ_ATTN_STAMP_FLUSH(stamps, (blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) * 4 + w);
   return p;
+}
+
+// The head: the body's form for the cache length, chosen once (uniform over the launch).
+template <int DT, int D, bool STREAMS = false, bool VERIFY = false, bool PAGED = false, bool KV8 = false>
+__device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, int split, int hq, int b,
+                                                      const AttnLds<D> &S, int cb = 0, long long pv = 0,
+                                                      int page = 0, unsigned long long *stamps = nullptr) {
+  if (a.L <= kAttnSpecL) return decode_attn_body<DT, D, STREAMS, VERIFY, PAGED, KV8, true>(a, split, hq, b, S, cb, pv, page, stamps);
+  return decode_attn_body<DT, D, STREAMS, VERIFY, PAGED, KV8, false>(a, split, hq, b, S, cb, pv, page, stamps);
 }
 
 // The chunk of token row r that a per-stream kernel does not compute (its early exit, uniform over the

@@ -136,6 +136,24 @@ __device__ __forceinline__ float dq_scale(const ScaleSrc &s, long long b, float 
   return __fadd_rn(__fmul_rn(c, s.absmax2[b / s.bs2]), offset);
 }
 
+// Kernel arguments are read ONCE at entry and laundered through an empty asm:
+// the compiler then keeps them in SGPRs instead of re-fetching them from the
+// kernarg segment at each use (every re-fetch is a serialized scalar-cache miss
+// on the critical path of a ~us kernel).
+template <typename T> __device__ __forceinline__ T keep_s(T v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
+template <typename T> __device__ __forceinline__ T *keep_sp(T *v) {
+  // launder as a GLOBAL (address space 1) pointer so that loads through the
+  // result are still selected as global_load (a generic pointer would become
+  // flat_load, which drains both vmcnt and lgkmcnt at every wait)
+  typedef __attribute__((address_space(1))) T *gptr;
+  gptr g = (gptr)v;
+  asm volatile("" : "+s"(g));
+  return (T *)g;
+}
+
 inline bool valid_blocksize(int bs) {
   return bs == 64 || bs == 128 || bs == 256 || bs == 512 || bs == 1024 || bs == 2048 || bs == 4096;
 }

@@ -5,8 +5,10 @@
 // which the rocprofv3 tracer cannot resolve at a few microseconds.
 // Built with hidden visibility: only the qz_diag_* entry points are exported, so the
 // included product entry points of gemv.hip never clash with libquantizations.so.
+// Also the decode attention head (attn_core.h) with its seven stamps: scripts/attn_stamps.py.
 #define QZ_STAMPS 1
 #include "gemv.hip"
+#include "attn_core.h"
 
 #define QZ_DIAG_API extern "C" __attribute__((visibility("default")))
 
@@ -97,3 +99,44 @@ QZ_DIAG_API int qz_diag_grouped_norm_stamped(int M, int K, const void *x, const 
   return QZ_OK;
 }
 
+// k_decode_attn (layer_ops.hip) with the head's stamps: fp16, D = 128, one chunk (L <= kAttnChunk), B = 1.
+// 8 u64 per wave at stamps[(hq * 4 + wave) * 8]: 0 entry, 1 loads issued, 2 K in registers, 3 first
+// barrier passed, 4 V in registers, 5 P V done, 6 output store issued.
+__global__ __launch_bounds__(256) void k_diag_decode_attn(DecodeAttnArgs a, unsigned long long *stamps) {
+  constexpr int D = 128;
+  __shared__ __attribute__((aligned(16))) uint32_t s_v[kAttnChunk * (D / 2)];
+  __shared__ __attribute__((aligned(16))) unsigned char s_small[AttnLds<D>::kSmallBytes];
+  const AttnLds<D> S{s_v, s_small};
+  const long long p = decode_attn_head<QZ_DT_F16, D>(a, blockIdx.x, blockIdx.y, blockIdx.z, S, 0, 0, 0, stamps);
+  if (threadIdx.x == 0) {
+    const unsigned int total = gridDim.x * gridDim.y * gridDim.z;
+    if (atomicAdd(a.arrive, 1u) == total - 1u) {
+      if (p < a.L) *a.pos = p + 1;
+      atomicExch(a.arrive, 0u);
+    }
+  }
+}
+
+// qz_decode_attention for fp16, B = 1, D = 128, L <= 128, contiguous q / k / v rows and one cos / sin row;
+// stamps: Hq * 4 * 8 u64 (device).  The operands are the product entry point's.
+QZ_DIAG_API int qz_diag_decode_attn_stamped(int Hq, int Hkv, int L, const void *q, const void *k, const void *v,
+                                            const void *cos, const void *sin, void *k_cache, void *v_cache,
+                                            const void *mask, long long *pos, unsigned int *arrive, void *out,
+                                            float scale, unsigned long long *stamps, void *stream) {
+  constexpr int D = 128;
+  if (Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0 || Hq / Hkv > kAttnMaxG || L <= 0 || L > kAttnChunk) return QZ_ERR_SHAPE;
+  if (!q || !k || !v || !cos || !sin || !k_cache || !v_cache || !mask || !pos || !arrive || !out || !stamps)
+    return QZ_ERR_ARG;
+  if (((uintptr_t)k_cache | (uintptr_t)v_cache) % 16 != 0 || ((uintptr_t)v % 4) != 0) return QZ_ERR_ARG;
+  DecodeAttnArgs a{};
+  a.q = q; a.k = k; a.v = v; a.qs = (long long)Hq * D; a.ks = a.vs = (long long)Hkv * D;
+  a.cos = cos; a.sin = sin; a.cs = 0;
+  a.kc = k_cache; a.vc = v_cache;
+  a.mask = reinterpret_cast<const unsigned char *>(mask); a.mb = L; a.mj = 1;
+  a.pos = pos; a.arrive = arrive;
+  a.out = out; a.os = (long long)Hq * D; a.part = nullptr;
+  a.Hkv = Hkv; a.G = Hq / Hkv; a.L = L; a.nsplit = 1; a.scale = scale;
+  hipLaunchKernelGGL(k_diag_decode_attn, dim3(1, Hq, 1), dim3(256), 0, (hipStream_t)stream, a, stamps);
+  QZ_LAUNCH_CHECK();
+  return QZ_OK;
+}

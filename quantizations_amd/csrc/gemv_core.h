@@ -188,23 +188,7 @@ __device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float c) {
   return __builtin_amdgcn_fdot2(__builtin_bit_cast(h2_t, a), __builtin_bit_cast(h2_t, b), c, false);
 }
 
-// Kernel arguments are read ONCE at entry and laundered through an empty asm:
-// the compiler then keeps them in SGPRs instead of re-fetching them from the
-// kernarg segment at each use (every re-fetch is a serialized scalar-cache miss
-// on the critical path of a ~us kernel).
-template <typename T> __device__ __forceinline__ T keep_s(T v) {
-  asm volatile("" : "+s"(v));
-  return v;
-}
-template <typename T> __device__ __forceinline__ T *keep_sp(T *v) {
-  // launder as a GLOBAL (address space 1) pointer so that loads through the
-  // result are still selected as global_load (a generic pointer would become
-  // flat_load, which drains both vmcnt and lgkmcnt at every wait)
-  typedef __attribute__((address_space(1))) T *gptr;
-  gptr g = (gptr)v;
-  asm volatile("" : "+s"(g));
-  return (T *)g;
-}
+// (keep_s / keep_sp, the kernel-argument launderers, live in common.h: attn_core.h uses them too)
 
 // Diagnostic timeline stamps (measurement-only builds: diag_stamps.hip and scripts/microbench
 // define QZ_STAMPS and instantiate STAMP != 0).  The product library compiles none of this.  Per

@@ -232,9 +232,10 @@ __global__ __launch_bounds__(256) void k_decode_attn(DecodeAttnArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char s_small[AttnLds<D>::kSmallBytes];
   const AttnLds<D> S{s_v, s_small};
   const long long p = decode_attn_head<DT, D>(a, blockIdx.x, blockIdx.y, blockIdx.z, S);
-  // the last workgroup to arrive advances the cache position (every workgroup has read p)
-  __syncthreads();
-  if (threadIdx.x == 0 && (kAttnAbl & 1) == 0) {
+  // the last workgroup to arrive advances the cache position.  Every thread of every workgroup that
+  // has arrived has read p: a wave consumes p before the head's first workgroup barrier, and thread 0
+  // comes here only behind the head's last one.
+  if (threadIdx.x == 0) {
     const unsigned int total = gridDim.x * gridDim.y * gridDim.z;
     if (atomicAdd(a.arrive, 1u) == total - 1u) {
       if (p < a.L) *a.pos = p + 1;   // a full cache keeps its position (every later call is NaN too)

@@ -73,7 +73,11 @@ __global__ __launch_bounds__(256) void k_gemm_4bit(GemmParams p) {
   const int wr = tid >> 1, wh = tid & 1;
   const int wrow = min(m0 + wr, p.M - 1);  // clamped: rows >= M are computed and never stored
   const unsigned char *wptr = p.B + (size_t)wrow * row_bytes + 16 * wh;
-  const uint32_t blk_row = (uint32_t)(((long long)wrow * p.K) >> p.bs_log2);  // K % 64 == 0, blocksize >= 64
+  // flat scale block of (wrow, k0) = (wrow * K + k0) >> bs_log2: the row's first block plus the
+  // blocks that k0 crosses counted from the row's offset inside that block (a row starts
+  // mid-block whenever K % blocksize != 0).  K % 64 == 0 and blocksize >= 64: one block per step.
+  const uint32_t blk_row = (uint32_t)(((long long)wrow * p.K) >> p.bs_log2);
+  const uint32_t blk_rem = ((uint32_t)wrow * (uint32_t)p.K) & ((1u << p.bs_log2) - 1u);
 
   // ---- staged registers of one K-step ----
   v4u xv[XC];
@@ -90,7 +94,7 @@ __global__ __launch_bounds__(256) void k_gemm_4bit(GemmParams p) {
                       : v4u{0u, 0u, 0u, 0u};
     }
     wv = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(wptr + (k0 >> 1)));
-    const uint32_t b = blk_row + ((uint32_t)k0 >> p.bs_log2);
+    const uint32_t b = blk_row + ((blk_rem + (uint32_t)k0) >> p.bs_log2);
     if constexpr (DQ) {
       q = p.sc.qabsmax[b];
       a = p.sc.absmax2[b >> p.bs2_log2];
@@ -280,14 +284,20 @@ __global__ __launch_bounds__(512) void k_gemm_4bit_8p(GemmParams p) {
   const int wr = tid >> 1, wh = tid & 1;  // decode ownership: row wr, 32-code half wh
   const int wrow = min(m0 + wr, p.M - 1);
   const unsigned char *wptr = p.B + (size_t)wrow * ((uint32_t)p.K >> 1) + 16 * wh;
+  // flat scale block of (row, k0) = (row * K + k0) >> bs_log2, as in k_gemm_4bit: the row's first
+  // block, plus the blocks k0 crosses from the row's offset inside it.  The DMA (row srow) and the
+  // byte pick (row wr) use the one formula, so the byte comes from the dword that was fetched.
+  const uint32_t bs_mask = (1u << p.bs_log2) - 1u;
   const uint32_t blk_row = (uint32_t)(((long long)wrow * p.K) >> p.bs_log2);
-  const int srow = tid & 255;
-  const uint32_t blk_row_s = (uint32_t)(((long long)min(m0 + srow, p.M - 1) * p.K) >> p.bs_log2);
+  const uint32_t blk_rem = ((uint32_t)wrow * (uint32_t)p.K) & bs_mask;
+  const int srow = min(m0 + (tid & 255), p.M - 1);
+  const uint32_t blk_row_s = (uint32_t)(((long long)srow * p.K) >> p.bs_log2);
+  const uint32_t blk_rem_s = ((uint32_t)srow * (uint32_t)p.K) & bs_mask;
   auto dma_w = [&](int step, int slot) {
     const int k0 = step * kBK;
     __builtin_amdgcn_global_load_lds((glb_ptr_t)(wptr + (k0 >> 1)),
                                      (lds_ptr_t)(smem + k8pWp + slot * kBigWp + wave * 1024), 16, 0, 0);
-    const uint32_t b = blk_row_s + ((uint32_t)k0 >> p.bs_log2);
+    const uint32_t b = blk_row_s + ((blk_rem_s + (uint32_t)k0) >> p.bs_log2);
     const void *src;
     if constexpr (DQ)
       src = tid < 256 ? (const void *)(p.sc.qabsmax + (b & ~3u)) : (const void *)(p.sc.absmax2 + (b >> p.bs2_log2));
@@ -310,7 +320,7 @@ __global__ __launch_bounds__(512) void k_gemm_4bit_8p(GemmParams p) {
   auto make_table = [&](int step, const ScaleWords &sw, uint32_t (&t)[8]) {
     float am;
     if constexpr (DQ) {
-      const uint32_t b = blk_row + ((uint32_t)(step * kBK) >> p.bs_log2);
+      const uint32_t b = blk_row + ((blk_rem + (uint32_t)(step * kBK)) >> p.bs_log2);
       const uint32_t q = (sw.q >> (8 * (b & 3))) & 255u;
       am = __fadd_rn(__fmul_rn(s_code2[q], sw.a), offset);   // core.py:467-468
     } else {

@@ -783,6 +783,60 @@ int qz_gemm_4bit_grouped_lora(int nseg, const qz_gemv_segment *segs, const qz_lo
                               int t_stride, const int *slot, int tokens_per_slot, int T, int K, const void *X, int ldx,
                               int dtype, int quant_type, int blocksize, int blocksize2, void *stream);
 
+/* Routed mixture-of-experts decode (extension; MixtralSparseMoeBlock.forward of transformers 5.x for
+ * 1 <= T <= 16 token rows of F16/BF16 activations): three launches, none of which returns a value
+ * to the host -- the expert choice stays in device memory (idx, w), so the step can be captured.
+ * E <= 64 experts, 1 <= top_k <= min(E, 8), H % 256 == 0 and I % 256 == 0 (else QZ_ERR_SHAPE);
+ * a NULL operand, top_k > E, or both / neither of absmax and qabsmax is QZ_ERR_ARG; nothing is
+ * launched on an error.
+ *
+ * qz_moe_route -- MixtralTopKRouter.forward: per token t,
+ *   logit[e] = round(sum_k x[t,k] * router_w[e,k])   fp32 sums, rounded once to `dtype` (F.linear)
+ *   p        = softmax(logit) in fp32
+ *   idx[t,:] = the top_k largest p in descending order, a tie going to the lower expert index
+ *   w[t,s]   = p[idx[t,s]] / sum_s p[idx[t,s]]
+ * x [T, H] with row stride ldx (% 8 == 0, 16-B aligned), router_w [E, H] of `dtype` (16-B aligned),
+ * idx int32 [T, top_k], w fp32 [T, top_k]; logits ([T, E] of `dtype`, nullable) receives the
+ * rounded logits. */
+int qz_moe_route(int T, int H, int E, int top_k, const void *x, int ldx, int dtype, const void *router_w, int *idx,
+                 float *w, void *logits, void *stream);
+
+/* qz_moe_pair_silu_4bit -- act_fn(gate) * up of the chosen experts.  B is ONE flat-quantised tensor
+ * of E * 2I rows by H (MixtralExperts.gate_up_proj flattened; one QuantState): expert e's gate row m
+ * is row e * 2I + m, its up row is row e * 2I + I + m, and the scale block of a flat element is
+ * block_base + element / blocksize, as for every other consumer.  For every entry (t, s) with
+ * e = idx[t,s] in [0, E):
+ *   g = round(W_gate[e] x[t]), u = round(W_up[e] x[t])        fp32 accumulation, weights decoded to
+ *                                                             the values qz_dequantize_4bit stores
+ *   h[t,s,m] = round(round(g / (1 + exp(-g))) * u)            (qz_silu_mul's arithmetic)
+ * An idx entry outside [0, E) forms no address: its h row is written as zeros.  h is [T, top_k, I]
+ * of `dtype`, contiguous, 16-B aligned; every element of it is written.  The weights of an expert
+ * are read once however many tokens chose it, and not at all if none did.  h[t,s,:] has the same
+ * bits for any T, any row position t and any choices of the other rows. */
+int qz_moe_pair_silu_4bit(int T, int H, int I, int E, int top_k, const void *x, int ldx, int dtype,
+                          const unsigned char *B, int quant_type, int blocksize, const float *absmax,
+                          const unsigned char *qabsmax, const float *absmax2, const float *code2,
+                          const float *offset, int blocksize2, long long block_base, const int *idx, void *h,
+                          void *stream);
+
+/* qz_moe_down_4bit -- down projection of the chosen experts and their weighted sum.  B is the
+ * flat-quantised E * H rows by I (MixtralExperts.down_proj flattened); h is qz_moe_pair_silu_4bit's
+ * output.  Per token t and output row m:
+ *   d_s    = round(W_down[idx[t,s]] h[t,s])[m]                fp32 accumulation, rounded to `dtype`
+ *   y[t,m] = round(sum_s w[t,s] * d_s)
+ * The sum is fp32, starts at 0, and takes its terms (a rounded product, then a rounded add) in
+ * ascending expert index idx[t,s] -- the same expert named twice: in ascending s -- an order that
+ * depends on idx[t,:] alone; entries outside [0, E) contribute nothing.  With `residual` (contiguous
+ * [T, H] of `dtype`, nullable): y[t,m] = round(residual[t,m] + round(sum)), qz_gemv_4bit_residual's
+ * two roundings.  y has row stride ldy >= H.  No atomics: every element of y[0:T] is written exactly
+ * once per launch, so y needs no clearing.  y[t,:] has the same bits for any T, any row position t
+ * and any choices of the other rows. */
+int qz_moe_down_4bit(int T, int H, int I, int E, int top_k, const void *h, int dtype, const unsigned char *B,
+                     int quant_type, int blocksize, const float *absmax, const unsigned char *qabsmax,
+                     const float *absmax2, const float *code2, const float *offset, int blocksize2,
+                     long long block_base, const int *idx, const float *w, const void *residual, void *y, int ldy,
+                     void *stream);
+
 /* The launch-geometry measurement knobs in effect (QZ_GEMV_WIDE8, QZ_GROUPED_NORM_R,
  * QZ_GROUPED_NORM_NW8, QZ_PAIR_R, QZ_PAIR_WT, QZ_PAIR_PS, QZ_PAIR_WK1, and QZ_GEMM16_SCHED -- the schedule qz_gemm_16bit (default 971, persistent)
  * launches: environment variables read ONCE when the library is loaded) and the

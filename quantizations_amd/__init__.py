@@ -21,6 +21,8 @@ from .core import (  # noqa: F401
 )
 from .autograd import MatMul4Bit  # noqa: F401
 from .modules import Linear4bit, matmul_4bit  # noqa: F401
+from .moe import SparseMoe4bit  # noqa: F401
+from .integration import replace_moe_blocks  # noqa: F401
 from .generation import (  # noqa: F401
     DecodeSession,
     GenerateOutput,

@@ -855,3 +855,99 @@ def gemm_4bit_grouped(A: Tensor, items, lora=None) -> list:
                                        dtype_code(A.dtype), _lib.QUANT_TYPES[s0.quant_type], s0.blocksize, bs2,
                                        _lib.stream_of(A)), "gemm_4bit_grouped")
     return [y.reshape(*lead, y.shape[-1]) for y in outs]
+
+
+# ---------------------------------------------------------------------------
+# routed mixture-of-experts decode (csrc/moe.hip): 1..16 token rows, the expert choice stays on
+# the device.  Each binding returns None where the library answers QZ_ERR_SHAPE (the caller runs
+# its composed form); any other failure raises.
+def _moe_rows(A: Tensor, K: int) -> Tensor:
+    A2 = A.reshape(-1, K)
+    if A2.stride(-1) != 1 or A2.stride(0) % 8 != 0 or A2.data_ptr() % 16 != 0:
+        A2 = A2.contiguous()
+    return A2
+
+
+def _moe_routing(idx: Tensor, w: Optional[Tensor], T: int, dev, what: str) -> int:
+    """Validate the routing table for T rows; returns top_k."""
+    if idx.dim() != 2 or idx.shape[0] != T or idx.dtype != torch.int32 or not idx.is_contiguous() or idx.device != dev:
+        raise ValueError(f"{what}: idx must be a contiguous int32 [{T}, top_k] tensor on the input's device")
+    if w is not None and (w.shape != idx.shape or w.dtype != torch.float32 or not w.is_contiguous()
+                          or w.device != dev):
+        raise ValueError(f"{what}: w must be a contiguous fp32 tensor of idx's shape on the input's device")
+    return int(idx.shape[1])
+
+
+def _moe_weight(B: Tensor, state: QuantState, E: int, K: int, what: str) -> int:
+    """Validate a stacked flat-quantised expert weight [E * rows, K]; returns rows."""
+    if len(state.shape) != 2 or state.shape[1] != K or state.shape[0] % E != 0 or \
+            B.numel() * 2 != state.shape[0] * K or not B.is_contiguous():
+        raise ValueError(f"{what}: the weight must be one flat-quantised [E * rows, {K}] tensor")
+    return state.shape[0] // E
+
+
+def moe_route(x: Tensor, router_weight: Tensor, top_k: int, logits: bool = False):
+    """MixtralTopKRouter.forward on 1..16 rows x [T, H] (qz_moe_route): (idx int32 [T, top_k],
+    w fp32 [T, top_k][, logits [T, E]]).  None for what the kernel does not take."""
+    E, H = router_weight.shape
+    if x.dtype not in (torch.float16, torch.bfloat16) or router_weight.dtype != x.dtype or x.shape[-1] != H or \
+            router_weight.device != x.device:
+        return None
+    x2 = _moe_rows(x, H)
+    T = x2.shape[0]
+    rw = router_weight.contiguous()
+    idx = torch.empty((T, top_k), dtype=torch.int32, device=x.device)
+    w = torch.empty((T, top_k), dtype=torch.float32, device=x.device)
+    lg = torch.empty((T, E), dtype=x.dtype, device=x.device) if logits else None
+    rc = lib.qz_moe_route(T, H, E, int(top_k), ptr(x2), x2.stride(0), dtype_code(x.dtype), ptr(rw), ptr(idx), ptr(w),
+                          ptr(lg), _lib.stream_of(x))
+    if rc == _lib.QZ_ERR_SHAPE:
+        return None
+    check(rc, "moe_route")
+    return (idx, w, lg) if logits else (idx, w)
+
+
+def moe_pair_silu(x: Tensor, B: Tensor, state: QuantState, idx: Tensor, E: int) -> Optional[Tensor]:
+    """h [T, top_k, I] = F.silu(gate) * up of expert idx[t, s] on row x[t], for the stacked
+    flat-quantised gate_up weight B [E * 2I, H] (qz_moe_pair_silu_4bit).  An idx entry outside
+    [0, E) gives a zero row.  None for what the kernel does not take."""
+    H = x.shape[-1]
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        return None
+    rows = _moe_weight(B, state, E, H, "moe_pair_silu")
+    x2 = _moe_rows(x, H)
+    T = x2.shape[0]
+    top_k = _moe_routing(idx, None, T, x.device, "moe_pair_silu")
+    h = torch.empty((T, top_k, rows // 2), dtype=x.dtype, device=x.device)
+    rc = lib.qz_moe_pair_silu_4bit(T, H, rows // 2, E, top_k, ptr(x2), x2.stride(0), dtype_code(x.dtype), ptr(B),
+                                   _lib.QUANT_TYPES[state.quant_type], state.blocksize, *state.scale_args(), 0,
+                                   ptr(idx), ptr(h), _lib.stream_of(x))
+    if rc == _lib.QZ_ERR_SHAPE:
+        return None
+    check(rc, "moe_pair_silu")
+    return h
+
+
+def moe_down(h: Tensor, B: Tensor, state: QuantState, idx: Tensor, w: Tensor, E: int,
+             residual: Optional[Tensor] = None) -> Optional[Tensor]:
+    """y [T, H] = sum_s w[t, s] * (W_down[idx[t, s]] h[t, s]) (+ residual [T, H]) for the stacked
+    flat-quantised down weight B [E * H, I] (qz_moe_down_4bit); entries of idx outside [0, E) add
+    nothing.  None for what the kernel does not take."""
+    if h.dim() != 3 or h.dtype not in (torch.float16, torch.bfloat16) or not h.is_contiguous():
+        return None
+    T, _, I = h.shape
+    H = _moe_weight(B, state, E, I, "moe_down")
+    top_k = _moe_routing(idx, w, T, h.device, "moe_down")
+    if top_k != h.shape[1]:
+        raise ValueError("moe_down: h must be [T, top_k, I] for idx [T, top_k]")
+    if residual is not None and (residual.dtype != h.dtype or residual.numel() != T * H or
+                                 not residual.is_contiguous() or residual.device != h.device):
+        raise ValueError(f"moe_down: residual must be a contiguous {h.dtype} tensor of {T * H} elements")
+    y = torch.empty((T, H), dtype=h.dtype, device=h.device)
+    rc = lib.qz_moe_down_4bit(T, H, I, E, top_k, ptr(h), dtype_code(h.dtype), ptr(B),
+                              _lib.QUANT_TYPES[state.quant_type], state.blocksize, *state.scale_args(), 0, ptr(idx),
+                              ptr(w), ptr(residual), ptr(y), H, _lib.stream_of(h))
+    if rc == _lib.QZ_ERR_SHAPE:
+        return None
+    check(rc, "moe_down")
+    return y

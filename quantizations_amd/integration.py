@@ -63,6 +63,29 @@ def replace_with_bnb_linear(model: nn.Module, modules_to_not_convert: Optional[I
 _replace_with_bnb_linear = replace_with_bnb_linear
 
 
+# mixture-of-experts blocks whose forward is MixtralSparseMoeBlock's of transformers 5.x: gate =
+# a top-k softmax router with a dense [E, H] weight, experts = stacked gate_up_proj / down_proj
+MOE_BLOCK_CLASSES = ("MixtralSparseMoeBlock",)
+
+
+def replace_moe_blocks(model: nn.Module, quant_type: str = "nf4", compress_statistics: bool = True,
+                       blocksize: int = 64) -> nn.Module:
+    """Replace every mixture-of-experts block (MOE_BLOCK_CLASSES, matched by class name) with a
+    moe.SparseMoe4bit built from its parameters: the stacked expert weights, which
+    replace_with_bnb_linear does not see (they are nn.Parameters, not nn.Linear children), become
+    4-bit; the router stays dense.  The weights must be on a GPU.  Returns the model."""
+    from .moe import SparseMoe4bit
+
+    for parent in list(model.modules()):
+        for name, child in list(parent.named_children()):
+            if type(child).__name__ not in MOE_BLOCK_CLASSES:
+                continue
+            parent._modules[name] = SparseMoe4bit(child.gate.weight.data, child.experts.gate_up_proj.data,
+                                                  child.experts.down_proj.data, child.top_k, quant_type=quant_type,
+                                                  compress_statistics=compress_statistics, blocksize=blocksize)
+    return model
+
+
 # projections of one block that read the same input (Llama/Mistral/Qwen naming,
 # plus the Mixtral-style w1/w3 expert pair)
 DEFAULT_PROJECTION_GROUPS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"), ("w1", "w3"))

@@ -837,6 +837,47 @@ int qz_moe_down_4bit(int T, int H, int I, int E, int top_k, const void *h, int d
                      long long block_base, const int *idx, const float *w, const void *residual, void *y, int ldy,
                      void *stream);
 
+/* Routed mixture-of-experts above 16 rows (prompts, prefill chunks, scoring, wide batches): four
+ * entry points, route -> plan -> gate/up/SiLU -> down, none of which returns a value to the host.
+ * 1 <= T <= 65536 rows and T * top_k <= 131072 routing entries per call (else QZ_ERR_SHAPE: the
+ * caller splits by rows, which changes no bit of any row); the other limits and the error codes are
+ * those of the three decode entry points above.  A row of h or y has the same bits in any launch:
+ * whatever T is, wherever the row stands and whatever the other rows choose.
+ *
+ * qz_moe_route_rows -- qz_moe_route for up to 65536 rows: the same kernel and operands, so a row's
+ * idx / w / logits are the bits qz_moe_route gives that row. */
+int qz_moe_route_rows(int T, int H, int E, int top_k, const void *x, int ldx, int dtype, const void *router_w,
+                      int *idx, float *w, void *logits, void *stream);
+
+/* qz_moe_plan -- the routing entries j = t * top_k + s of idx [T, top_k] sorted by expert, stable:
+ *   sorted[offsets[e] : offsets[e+1]]  the entries with idx == e, in ascending j        (e < E)
+ *   sorted[offsets[E] : offsets[E+1]]  the entries outside [0, E), in ascending j; offsets[E+1] == n
+ * sorted int32 [T * top_k], offsets int32 [E + 2].  One workgroup, no atomics; the result depends on
+ * idx alone. */
+int qz_moe_plan(int T, int E, int top_k, const int *idx, int *sorted, int *offsets, void *stream);
+
+/* qz_moe_gemm_pair_silu_4bit -- qz_moe_pair_silu_4bit's h [T, top_k, I] (same B, same arithmetic per
+ * element: fp32 sums over K, both projections rounded, qz_silu_mul's epilogue) as one expert-grouped
+ * tile GEMM over the plan (sorted, offsets) of idx.  The rows of entries outside [0, E) are written
+ * as zeros; every element of h is written.  No split-K. */
+int qz_moe_gemm_pair_silu_4bit(int T, int H, int I, int E, int top_k, const void *x, int ldx, int dtype,
+                               const unsigned char *B, int quant_type, int blocksize, const float *absmax,
+                               const unsigned char *qabsmax, const float *absmax2, const float *code2,
+                               const float *offset, int blocksize2, long long block_base, const int *sorted,
+                               const int *offsets, void *h, void *stream);
+
+/* qz_moe_gemm_down_4bit -- qz_moe_down_4bit's y in two launches: the grouped tile GEMM stores
+ * d[j, :] = round(W_down[idx[j]] h[j]) for every entry j with an expert into the caller's workspace
+ * d ([T * top_k, H] of `dtype`, 16-B aligned, need not be cleared), then one thread per 8 outputs
+ * folds y[t,m] = round(sum_s w[t,s] * d[t * top_k + s, m]) in ascending (expert, slot) with a rounded
+ * product and a rounded add per term, and with `residual` stores round(residual + round(sum)).
+ * y (16-B aligned) has row stride ldy >= H, ldy % 8 == 0; every element of y[0:T] is written once. */
+int qz_moe_gemm_down_4bit(int T, int H, int I, int E, int top_k, const void *h, int dtype, const unsigned char *B,
+                          int quant_type, int blocksize, const float *absmax, const unsigned char *qabsmax,
+                          const float *absmax2, const float *code2, const float *offset, int blocksize2,
+                          long long block_base, const int *idx, const float *w, const int *sorted,
+                          const int *offsets, void *d, const void *residual, void *y, int ldy, void *stream);
+
 /* The launch-geometry measurement knobs in effect (QZ_GEMV_WIDE8, QZ_GROUPED_NORM_R,
  * QZ_GROUPED_NORM_NW8, QZ_PAIR_R, QZ_PAIR_WT, QZ_PAIR_PS, QZ_PAIR_WK1, and QZ_GEMM16_SCHED -- the schedule qz_gemm_16bit (default 971, persistent)
  * launches: environment variables read ONCE when the library is loaded) and the

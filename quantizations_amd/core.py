@@ -886,9 +886,7 @@ def _moe_weight(B: Tensor, state: QuantState, E: int, K: int, what: str) -> int:
     return state.shape[0] // E
 
 
-def moe_route(x: Tensor, router_weight: Tensor, top_k: int, logits: bool = False):
-    """MixtralTopKRouter.forward on 1..16 rows x [T, H] (qz_moe_route): (idx int32 [T, top_k],
-    w fp32 [T, top_k][, logits [T, E]]).  None for what the kernel does not take."""
+def _moe_route(entry: str, x: Tensor, router_weight: Tensor, top_k: int, logits: bool):
     E, H = router_weight.shape
     if x.dtype not in (torch.float16, torch.bfloat16) or router_weight.dtype != x.dtype or x.shape[-1] != H or \
             router_weight.device != x.device:
@@ -899,12 +897,18 @@ def moe_route(x: Tensor, router_weight: Tensor, top_k: int, logits: bool = False
     idx = torch.empty((T, top_k), dtype=torch.int32, device=x.device)
     w = torch.empty((T, top_k), dtype=torch.float32, device=x.device)
     lg = torch.empty((T, E), dtype=x.dtype, device=x.device) if logits else None
-    rc = lib.qz_moe_route(T, H, E, int(top_k), ptr(x2), x2.stride(0), dtype_code(x.dtype), ptr(rw), ptr(idx), ptr(w),
-                          ptr(lg), _lib.stream_of(x))
+    rc = getattr(lib, entry)(T, H, E, int(top_k), ptr(x2), x2.stride(0), dtype_code(x.dtype), ptr(rw), ptr(idx),
+                             ptr(w), ptr(lg), _lib.stream_of(x))
     if rc == _lib.QZ_ERR_SHAPE:
         return None
-    check(rc, "moe_route")
+    check(rc, entry)
     return (idx, w, lg) if logits else (idx, w)
+
+
+def moe_route(x: Tensor, router_weight: Tensor, top_k: int, logits: bool = False):
+    """MixtralTopKRouter.forward on 1..16 rows x [T, H] (qz_moe_route): (idx int32 [T, top_k],
+    w fp32 [T, top_k][, logits [T, E]]).  None for what the kernel does not take."""
+    return _moe_route("qz_moe_route", x, router_weight, top_k, logits)
 
 
 def moe_pair_silu(x: Tensor, B: Tensor, state: QuantState, idx: Tensor, E: int) -> Optional[Tensor]:
@@ -950,4 +954,89 @@ def moe_down(h: Tensor, B: Tensor, state: QuantState, idx: Tensor, w: Tensor, E:
     if rc == _lib.QZ_ERR_SHAPE:
         return None
     check(rc, "moe_down")
+    return y
+
+
+# ---------------------------------------------------------------------------
+# routed mixture-of-experts above 16 rows (csrc/moe_prefill.hip): route -> plan -> the two
+# expert-grouped tile GEMMs.  Nothing comes back to the host, so the chain can be captured.  Each
+# binding returns None where the library answers QZ_ERR_SHAPE, as its decode twin does.
+MOE_MAX_ROWS = 65536      # kMoeMaxRows: rows of one launch
+MOE_MAX_ENTRIES = 131072  # kMoeMaxPlan: routing entries T * top_k of one plan
+
+
+def moe_route_rows(x: Tensor, router_weight: Tensor, top_k: int, logits: bool = False):
+    """moe_route for up to 65536 rows (qz_moe_route_rows: the same kernel, the same bits per row)."""
+    return _moe_route("qz_moe_route_rows", x, router_weight, top_k, logits)
+
+
+def moe_plan(idx: Tensor, E: int):
+    """(sorted int32 [T * top_k], offsets int32 [E + 2]): the entries t * top_k + s of idx grouped by
+    expert in ascending order, entries outside [0, E) as a last segment (qz_moe_plan)."""
+    if idx.dim() != 2 or idx.dtype != torch.int32 or not idx.is_contiguous() or not idx.is_cuda:
+        raise ValueError("moe_plan: idx must be a contiguous int32 [T, top_k] tensor on a GPU")
+    T, top_k = idx.shape
+    srt = torch.empty(T * top_k, dtype=torch.int32, device=idx.device)
+    offsets = torch.empty(E + 2, dtype=torch.int32, device=idx.device)
+    rc = lib.qz_moe_plan(T, E, top_k, ptr(idx), ptr(srt), ptr(offsets), _lib.stream_of(idx))
+    if rc == _lib.QZ_ERR_SHAPE:
+        return None
+    check(rc, "moe_plan")
+    return srt, offsets
+
+
+def _moe_plan_ok(plan, n: int, E: int, dev, what: str):
+    srt, offsets = plan
+    for t, size in ((srt, n), (offsets, E + 2)):
+        if t.dtype != torch.int32 or t.numel() != size or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{what}: plan must be moe_plan's (sorted [{n}], offsets [{E + 2}]) for this idx")
+    return srt, offsets
+
+
+def moe_gemm_pair_silu(x: Tensor, B: Tensor, state: QuantState, idx: Tensor, plan, E: int) -> Optional[Tensor]:
+    """moe_pair_silu's h [T, top_k, I] for any number of rows, as one expert-grouped tile GEMM over
+    plan = moe_plan(idx, E) (qz_moe_gemm_pair_silu_4bit)."""
+    H = x.shape[-1]
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        return None
+    rows = _moe_weight(B, state, E, H, "moe_gemm_pair_silu")
+    x2 = _moe_rows(x, H)
+    T = x2.shape[0]
+    top_k = _moe_routing(idx, None, T, x.device, "moe_gemm_pair_silu")
+    srt, offsets = _moe_plan_ok(plan, T * top_k, E, x.device, "moe_gemm_pair_silu")
+    h = torch.empty((T, top_k, rows // 2), dtype=x.dtype, device=x.device)
+    rc = lib.qz_moe_gemm_pair_silu_4bit(T, H, rows // 2, E, top_k, ptr(x2), x2.stride(0), dtype_code(x.dtype), ptr(B),
+                                        _lib.QUANT_TYPES[state.quant_type], state.blocksize, *state.scale_args(), 0,
+                                        ptr(srt), ptr(offsets), ptr(h), _lib.stream_of(x))
+    if rc == _lib.QZ_ERR_SHAPE:
+        return None
+    check(rc, "moe_gemm_pair_silu")
+    return h
+
+
+def moe_gemm_down(h: Tensor, B: Tensor, state: QuantState, idx: Tensor, w: Tensor, plan, E: int,
+                  residual: Optional[Tensor] = None) -> Optional[Tensor]:
+    """moe_down's y [T, H] for any number of rows: the grouped tile GEMM into a [T * top_k, H]
+    workspace, then the weighted sum per token in the decode kernel's order and roundings
+    (qz_moe_gemm_down_4bit)."""
+    if h.dim() != 3 or h.dtype not in (torch.float16, torch.bfloat16) or not h.is_contiguous():
+        return None
+    T, _, I = h.shape
+    H = _moe_weight(B, state, E, I, "moe_gemm_down")
+    top_k = _moe_routing(idx, w, T, h.device, "moe_gemm_down")
+    if top_k != h.shape[1]:
+        raise ValueError("moe_gemm_down: h must be [T, top_k, I] for idx [T, top_k]")
+    srt, offsets = _moe_plan_ok(plan, T * top_k, E, h.device, "moe_gemm_down")
+    if residual is not None and (residual.dtype != h.dtype or residual.numel() != T * H or
+                                 not residual.is_contiguous() or residual.device != h.device):
+        raise ValueError(f"moe_gemm_down: residual must be a contiguous {h.dtype} tensor of {T * H} elements")
+    d = torch.empty((T * top_k, H), dtype=h.dtype, device=h.device)
+    y = torch.empty((T, H), dtype=h.dtype, device=h.device)
+    rc = lib.qz_moe_gemm_down_4bit(T, H, I, E, top_k, ptr(h), dtype_code(h.dtype), ptr(B),
+                                   _lib.QUANT_TYPES[state.quant_type], state.blocksize, *state.scale_args(), 0,
+                                   ptr(idx), ptr(w), ptr(srt), ptr(offsets), ptr(d), ptr(residual), ptr(y), H,
+                                   _lib.stream_of(h))
+    if rc == _lib.QZ_ERR_SHAPE:
+        return None
+    check(rc, "moe_gemm_down")
     return y

@@ -3,6 +3,7 @@
 //
 //   k_moe_route      one workgroup per token: E router dot products (waves split H), softmax,
 //                    top-k, renormalised weights -> idx int32 [T, top_k], w fp32 [T, top_k]
+//                    (also launched for more rows: qz_moe_route_rows, for moe_prefill.hip)
 //   k_moe_pair_silu  grid (I / 16, E): the workgroup of (row block, expert e) compacts the routing
 //                    entries (t, s) with idx[t, s] == e and leaves at once if there are none;
 //                    otherwise 16 gate rows and 16 up rows of expert e meet the gathered token
@@ -20,28 +21,14 @@
 // workgroup reads and WHICH activation row a B column carries, both read from the routing table on
 // the device: a column's sums never depend on its position, on T or on its neighbours, so a token's
 // output bits are those of the token launched alone (there is no T = 1 specialisation).
-#include "gemm_common.h"
+#include "moe_common.h"
 
 namespace qz {
 
 constexpr int kMoeWaves = 8;                  // waves of an expert workgroup: they split K
 constexpr int kMoeXRow = kMtChunk * 2 + 16;   // padded LDS row of one column's chunk of activations
-constexpr int kMoeMaxE = 64, kMoeMaxTopK = 8, kMoeMaxT = 16;
+constexpr int kMoeMaxT = 16;
 constexpr int kMoeMaxEntries = kMoeMaxT * kMoeMaxTopK;   // routing entries (t, s) of one launch
-
-// v rounded to the storage format of DT (store_f32's conversions), back as fp32
-template <int DT> __device__ __forceinline__ float round16(float v) {
-  if constexpr (DT == QZ_DT_F16) return __half2float(__ushort_as_half(f32_to_f16_bits(v)));
-  else return __bfloat162float(__float2bfloat16(v));
-}
-
-// one stacked flat-quantised weight ([E * rows, K], one QuantState)
-struct MoeWeight {
-  const unsigned char *B;
-  ScaleSrc sc;
-  long long block_base;
-  int bs_log2, bs2_log2;
-};
 
 struct MoeArgs {
   MoeWeight wt;
@@ -391,11 +378,13 @@ __global__ __launch_bounds__(256) void k_moe_route(const void *x, int ldx, const
 
 using namespace qz;
 
-extern "C" int qz_moe_route(int T, int H, int E, int top_k, const void *x, int ldx, int dtype, const void *router_w,
-                            int *idx, float *w, void *logits, void *stream) {
+// qz_moe_route (1..16 rows, the decode step) and qz_moe_route_rows (any number up to kMoeMaxRows)
+// launch the one kernel: a row's idx / w / logits bits do not depend on the entry point
+static int route_launch(int max_T, int T, int H, int E, int top_k, const void *x, int ldx, int dtype,
+                        const void *router_w, int *idx, float *w, void *logits, void *stream) {
   if (!x || !router_w || !idx || !w || E < 1 || top_k < 1 || top_k > E) return QZ_ERR_ARG;
   if (dtype != QZ_DT_F16 && dtype != QZ_DT_BF16) return QZ_ERR_DTYPE;
-  if (T < 1 || T > kMoeMaxT || E > kMoeMaxE || top_k > kMoeMaxTopK || H < 256 || (H % 256) != 0 || ldx < H ||
+  if (T < 1 || T > max_T || E > kMoeMaxE || top_k > kMoeMaxTopK || H < 256 || (H % 256) != 0 || ldx < H ||
       (ldx % 8) != 0 || (reinterpret_cast<uintptr_t>(x) % 16) != 0 || (reinterpret_cast<uintptr_t>(router_w) % 16) != 0)
     return QZ_ERR_SHAPE;
   hipStream_t s = (hipStream_t)stream;
@@ -405,6 +394,16 @@ extern "C" int qz_moe_route(int T, int H, int E, int top_k, const void *x, int l
   });
   QZ_LAUNCH_CHECK();
   return QZ_OK;
+}
+
+extern "C" int qz_moe_route(int T, int H, int E, int top_k, const void *x, int ldx, int dtype, const void *router_w,
+                            int *idx, float *w, void *logits, void *stream) {
+  return route_launch(kMoeMaxT, T, H, E, top_k, x, ldx, dtype, router_w, idx, w, logits, stream);
+}
+
+extern "C" int qz_moe_route_rows(int T, int H, int E, int top_k, const void *x, int ldx, int dtype,
+                                 const void *router_w, int *idx, float *w, void *logits, void *stream) {
+  return route_launch(kMoeMaxRows, T, H, E, top_k, x, ldx, dtype, router_w, idx, w, logits, stream);
 }
 
 // the checks both expert launches share; fills a.wt and the routing geometry

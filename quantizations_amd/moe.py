@@ -7,11 +7,13 @@ over the 2-D view ``[E * rows, K]`` with one ``QuantState``; expert e is the row
 ``[e * rows, (e + 1) * rows)`` of it.
 
 Dispatch: up to 16 rows of fp16 / bf16 on the GPU run three launches -- route, gate/up/SiLU of the
-hit experts, down projection with the weighted sum (csrc/moe.hip) -- with the expert choice kept in
-device memory, so the block can be captured in a graph.  Anything else (prefill, fp32, shapes off the
-kernels' grid) runs the composed form with the same semantics: the host loop over hit experts, each
-dequantised on its row range and applied with ``F.linear``.  Inference only: an input that requires
-grad raises.
+hit experts, down projection with the weighted sum (csrc/moe.hip); more rows (prompts, prefill
+chunks, scoring passes, wide batches) run route, a device-side plan that sorts the routing entries by
+expert, and two expert-grouped tile GEMMs (csrc/moe_prefill.hip).  Both keep the expert choice in
+device memory, so the block never synchronises and can be captured in a graph.  Anything else (fp32,
+shapes off the kernels' grid, ``prefill_route = "composed"``) runs the composed form with the same
+semantics: the host loop over hit experts, each dequantised on its row range and applied with
+``F.linear``.  Inference only: an input that requires grad raises.
 """
 from __future__ import annotations
 
@@ -19,7 +21,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .core import (MT_MAX_TOKENS, Params4bit, QuantState, dequantize_4bit, moe_down, moe_pair_silu, moe_route)
+from .core import (MOE_MAX_ENTRIES, MOE_MAX_ROWS, MT_MAX_TOKENS, Params4bit, QuantState, dequantize_4bit, moe_down,
+                   moe_gemm_down, moe_gemm_pair_silu, moe_pair_silu, moe_plan, moe_route, moe_route_rows)
 from .modules import grad_route
 
 
@@ -75,6 +78,9 @@ class SparseMoe4bit(nn.Module):
         self.down_proj = quantised(down_proj)
 
     _EXPERT_PARAMS = ("gate_up_proj", "down_proj")
+    # inputs of more than 16 rows: "auto" = the grouped tile GEMMs where they take the shape,
+    # "composed" = always the host loop (kept reachable for timing and comparison)
+    prefill_route = "auto"
 
     def forward(self, hidden_states: torch.Tensor) -> torch.Tensor:
         if grad_route(hidden_states):
@@ -83,8 +89,13 @@ class SparseMoe4bit(nn.Module):
             raise RuntimeError("SparseMoe4bit weights are not quantised yet: move the module to a GPU first")
         x = hidden_states.reshape(-1, self.hidden_dim)
         y = None
-        if x.is_cuda and 1 <= x.shape[0] <= MT_MAX_TOKENS and x.dtype in (torch.float16, torch.bfloat16):
-            y = self._routed(x)
+        if self.prefill_route not in ("auto", "composed"):
+            raise ValueError(f"SparseMoe4bit.prefill_route must be 'auto' or 'composed', not {self.prefill_route!r}")
+        if x.is_cuda and x.shape[0] >= 1 and x.dtype in (torch.float16, torch.bfloat16):
+            if x.shape[0] <= MT_MAX_TOKENS:
+                y = self._routed(x)
+            elif self.prefill_route == "auto":
+                y = self._grouped(x)
         if y is None:
             y = self._composed(x)
         return y.reshape(hidden_states.shape)
@@ -100,6 +111,29 @@ class SparseMoe4bit(nn.Module):
         if h is None:
             return None
         return moe_down(h, self.down_proj, self.down_proj.quant_state, idx, w, E)
+
+    def _grouped(self, x):
+        """More than 16 rows: route_rows, plan and the two grouped tile GEMMs, in row chunks of what one
+        plan takes (a row has the same bits in any chunk); None where a launch declines the shape."""
+        E = self.num_experts
+        step = min(MOE_MAX_ROWS, MOE_MAX_ENTRIES // self.top_k)
+        out = []
+        for xc in x.split(step):
+            r = moe_route_rows(xc, self.gate.weight, self.top_k)
+            if r is None:
+                return None
+            idx, w = r
+            plan = moe_plan(idx, E)
+            if plan is None:
+                return None
+            h = moe_gemm_pair_silu(xc, self.gate_up_proj, self.gate_up_proj.quant_state, idx, plan, E)
+            if h is None:
+                return None
+            y = moe_gemm_down(h, self.down_proj, self.down_proj.quant_state, idx, w, plan, E)
+            if y is None:
+                return None
+            out.append(y)
+        return out[0] if len(out) == 1 else torch.cat(out)
 
     def _composed(self, x):
         """The same semantics from torch ops: MixtralTopKRouter, then the host loop over hit experts with

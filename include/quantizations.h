@@ -187,6 +187,25 @@ int qz_gemm_4bit(int T, int M, int K, const void *X, int ldx, int dtype, const u
 int qz_gemm_4bit_grouped(int nseg, const qz_gemv_segment *segs, int T, int K, const void *X, int ldx, int dtype,
                          int quant_type, int blocksize, int blocksize2, void *stream);
 
+/* Wide multi-token GEMM (17 <= T <= 64 rows, K % 256 == 0): batched decode and speculative verify
+ * steps past the 16-row kernel, in one read of the weights and without a workspace.  The weight
+ * fragments of a 256-element chunk are decoded once and multiplied against ceil(T / 16) blocks of
+ * 16 rows.  Row c of Y has exactly the bits qz_gemm_4bit gives that row in a launch of 2..16 rows,
+ * whatever T, c and the other rows are.  Arguments as qz_gemm_4bit, with block_base (as in
+ * qz_gemv_4bit) in the workspace's place; M % 4 == 0, blocksize >= 64, ldx % 8 == 0, ldy >= M,
+ * 16-B-aligned X and B.  Any other T (16 and 65 included) or K returns QZ_ERR_SHAPE: nothing is
+ * clamped and nothing is launched. */
+int qz_gemm_4bit_mt_wide(int T, int M, int K, const void *X, int ldx, int dtype, const unsigned char *B,
+                         int quant_type, int blocksize, const float *absmax, const unsigned char *qabsmax,
+                         const float *absmax2, const float *code2, const float *offset, int blocksize2,
+                         long long block_base, const void *bias, void *Y, int ldy, void *stream);
+
+/* qz_gemm_4bit_grouped for 17 <= T <= 64: 1..QZ_GEMV_MAX_SEGMENTS weights that share X in one grid.
+ * Segment i writes y_i[T, M_i] (row stride M_i), bit-identical to qz_gemm_4bit_mt_wide on that
+ * segment alone.  Other T / K return QZ_ERR_SHAPE. */
+int qz_gemm_4bit_grouped_wide(int nseg, const qz_gemv_segment *segs, int T, int K, const void *X, int ldx, int dtype,
+                              int quant_type, int blocksize, int blocksize2, void *stream);
+
 /* Dense 16-bit GEMM Y[T,M] = X[T,K] . W[M,K]^T (+ bias), fp32 accumulation
  * (v_mfma_f32_16x16x32_{f16,bf16}), on the same staggered 8-phase 256x256 schedule as the
  * fused kernel.  The large-T prefill route: qz_dequantize_4bit (bit-exact 16-bit weight,

@@ -13,6 +13,8 @@ from .core import (  # noqa: F401
     dequantize_blockwise,
     gemm_4bit,
     gemm_4bit_dgrad,
+    gemm_4bit_grouped_wide,
+    gemm_4bit_wide,
     gemv_4bit,
     get_4bit_type,
     get_ptr,
@@ -22,7 +24,7 @@ from .core import (  # noqa: F401
 from .autograd import MatMul4Bit  # noqa: F401
 from .modules import Linear4bit, matmul_4bit  # noqa: F401
 from .moe import SparseMoe4bit  # noqa: F401
-from .integration import replace_moe_blocks  # noqa: F401
+from .integration import replace_moe_blocks, set_decode_rows  # noqa: F401
 from .generation import (  # noqa: F401
     DecodeSession,
     GenerateOutput,

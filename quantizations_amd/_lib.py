@@ -117,6 +117,8 @@ SIGNATURES = {
     "qz_gemm_16bit": [_i, _i, _i, _p, _i, _i, _p, _p, _p, _i, _p],
     "qz_gemm_16bit_ok": [_i, _i, _i, _p, _i, _p, _p, _i],
     "qz_gemm_4bit_grouped": [_i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p],
+    "qz_gemm_4bit_mt_wide": [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _ll, _p, _p, _i, _p],
+    "qz_gemm_4bit_grouped_wide": [_i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p],
     "qz_moe_route": [_i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p],
     "qz_moe_pair_silu_4bit": [_i, _i, _i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _ll, _p, _p, _p],
     "qz_moe_down_4bit": [_i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _ll, _p, _p, _p, _p, _i, _p],

@@ -857,6 +857,81 @@ def gemm_4bit_grouped(A: Tensor, items, lora=None) -> list:
     return [y.reshape(*lead, y.shape[-1]) for y in outs]
 
 
+# Rows the wide multi-token kernel takes (csrc/gemm_mt_wide.hip): MT_MAX_TOKENS + 1 .. MT_WIDE_MAX_TOKENS.
+# Nothing routes there by itself: gemm_4bit_wide / gemm_4bit_grouped_wide are called by name, and
+# modules take them only with decode_rows raised (integration.set_decode_rows).
+MT_WIDE_MAX_TOKENS = 64
+
+
+def _wide_rows(A: Tensor):
+    """A as the [T, K] operand of the wide launches (a copy only where the kernel needs one)."""
+    K = A.shape[-1]
+    A2 = A.reshape(-1, K)
+    if A2.stride(-1) != 1 or A2.stride(0) % 8 != 0 or A2.stride(0) < K or A2.data_ptr() % 16 != 0:
+        A2 = A2.contiguous()
+    return A2
+
+
+def grouped_wide_ok(A: Tensor, items) -> bool:
+    """Whether gemm_4bit_grouped_wide can run `items` on A in one launch: 17..64 fp16/bf16 rows,
+    K % 256 == 0, 1..4 weights that share K, quant_type, blocksize (>= 64) and scale format, and
+    out_features % 4 == 0."""
+    K = A.shape[-1]
+    T = A.numel() // K if K else 0
+    if not (MT_MAX_TOKENS < T <= MT_WIDE_MAX_TOKENS and K % MT_K_MULTIPLE == 0 and A.is_cuda
+            and 1 <= len(items) <= _lib.GEMV_MAX_SEGMENTS and A.dtype in (torch.float16, torch.bfloat16)):
+        return False
+    s0 = items[0][1]
+    return s0.shape[1] == K and all(_same_format(s0, it[1]) and it[1].blocksize >= 64 and it[1].shape[0] % 4 == 0
+                                    for it in items)
+
+
+def gemm_4bit_grouped_wide(A: Tensor, items) -> list:
+    """gemm_4bit_grouped for 17..64 rows (qz_gemm_4bit_grouped_wide): several 4-bit weights that
+    share A in ONE launch that reads each weight once.  items: (B, state, bias[, block_base]);
+    returns [y_i] of shape [..., M_i].  Every row of every y_i has the bits gemm_4bit_grouped gives
+    that row in a launch of 2..16 rows.  grouped_wide_ok() says when it applies; no LoRA operand."""
+    items = list(items)
+    if not grouped_wide_ok(A, items):
+        raise ValueError(f"gemm_4bit_grouped_wide needs {MT_MAX_TOKENS + 1}..{MT_WIDE_MAX_TOKENS} fp16/bf16 rows on "
+                         "the GPU, K % 256 == 0, 1..4 weights that share K, quant_type, blocksize (>= 64) and scale "
+                         "format, and out_features % 4 == 0")
+    lead = A.shape[:-1]
+    A2 = _wide_rows(A)
+    T, K = A2.shape
+    segs, outs, _biases = _pack_segments([it[:4] for it in items], A.dtype,
+                                         lambda M: torch.empty((T, M), dtype=A.dtype, device=A.device),
+                                         "gemm_4bit_grouped_wide")
+    s0 = items[0][1]
+    bs2 = int(s0.state2.blocksize) if s0.nested else 0
+    check(lib.qz_gemm_4bit_grouped_wide(len(items), ctypes.cast(segs, ctypes.c_void_p), T, K, ptr(A2), A2.stride(0),
+                                        dtype_code(A.dtype), _lib.QUANT_TYPES[s0.quant_type], s0.blocksize, bs2,
+                                        _lib.stream_of(A)), "gemm_4bit_grouped_wide")
+    return [y.reshape(*lead, y.shape[-1]) for y in outs]
+
+
+def gemm_4bit_wide(A: Tensor, B: Tensor, state: QuantState, bias: Optional[Tensor] = None,
+                   block_base: int = 0) -> Tensor:
+    """A[..., K] . W^T (+ bias) for 17..64 rows on the wide multi-token kernel (qz_gemm_4bit_mt_wide):
+    one launch, one read of W, no workspace.  Row for row the bits of gemm_4bit on 2..16 of the
+    rows.  block_base: the weight's first scale block, for a row shard of a larger weight.
+    ValueError for any other row count (16 and 65 included), dtype or K."""
+    if not grouped_wide_ok(A, [(B, state, bias)]):
+        raise ValueError(f"gemm_4bit_wide needs {MT_MAX_TOKENS + 1}..{MT_WIDE_MAX_TOKENS} fp16/bf16 rows on the GPU, "
+                         "K % 256 == 0, blocksize >= 64 and out_features % 4 == 0")
+    M = state.shape[0]
+    lead = A.shape[:-1]
+    A2 = _wide_rows(A)
+    T, K = A2.shape
+    if bias is not None and (bias.dtype != A.dtype or not bias.is_contiguous()):
+        bias = bias.to(A.dtype).contiguous()
+    out = torch.empty((T, M), dtype=A.dtype, device=A.device)
+    check(lib.qz_gemm_4bit_mt_wide(T, M, K, ptr(A2), A2.stride(0), dtype_code(A.dtype), ptr(B),
+                                   _lib.QUANT_TYPES[state.quant_type], state.blocksize, *state.scale_args(),
+                                   int(block_base), ptr(bias), ptr(out), M, _lib.stream_of(A)), "gemm_4bit_wide")
+    return out.reshape(*lead, M)
+
+
 # ---------------------------------------------------------------------------
 # routed mixture-of-experts decode (csrc/moe.hip): 1..16 token rows, the expert choice stays on
 # the device.  Each binding returns None where the library answers QZ_ERR_SHAPE (the caller runs

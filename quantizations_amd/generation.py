@@ -545,7 +545,8 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
              max_matching_ngram_size: Optional[int] = None, prompt_lookup_sampling: bool = False,
              repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
              no_repeat_ngram_size=None, min_new_tokens=None, logprobs: Optional[int] = None,
-             constraint=None, constraint_start=None, logit_bias=None, suppress_tokens=None):
+             constraint=None, constraint_start=None, logit_bias=None, suppress_tokens=None,
+             decode_rows: Optional[int] = None):
     """input_ids [B, S] (equal-length prompts) followed by up to max_new_tokens picked tokens per
     stream: greedy, or with do_sample temperature / top_k / top_p (scalars or one per stream; a
     temperature <= 0 keeps that stream greedy) drawn from `generator` (a torch.Generator or a seed).
@@ -569,7 +570,9 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
     constraint (a TokenAutomaton) with constraint_start (a state, or one per stream; -1: that stream is
     unconstrained; None: the automaton's start): every pick is masked by its stream's state inside the
     step, with or without prompt lookup.  logit_bias ({token id: bias}, or one dict per stream; -inf
-    bans) and suppress_tokens (ids banned for every stream) are added in front of every pick."""
+    bans) and suppress_tokens (ids banned for every stream) are added in front of every pick.
+    decode_rows (None: as it was; 17..64): integration.set_decode_rows on the model, and with prompt
+    lookup up to that many rows per verify step instead of 16."""
     if input_ids.dim() != 2:
         raise ValueError("generate: input_ids must be [B, S]")
     _check_logprobs(logprobs, "generate")
@@ -596,7 +599,8 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
         sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator) if do_sample else None
         return _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attention_mask, graph,
                                      prompt_lookup_num_tokens, max_matching_ngram_size, sampling, penalties, logprobs,
-                                     constraint, constraint_start, bias)
+                                     constraint, constraint_start, bias, decode_rows)
+    _set_decode_rows(model, decode_rows)
     sess = DecodeSession(model, B, S + max_new_tokens, graph=graph, logprobs=logprobs, constraint=constraint,
                          logit_bias_slots=slots)
     _open_constraints(sess, bias)
@@ -702,6 +706,14 @@ class PagedKVCache:
                            "(_qz_paged); this forward took another path")
 
 
+def _set_decode_rows(model, decode_rows) -> None:
+    """The sessions' and generate()'s decode_rows keyword: None leaves the model alone."""
+    if decode_rows is not None:
+        from .integration import set_decode_rows
+
+        set_decode_rows(model, decode_rows)
+
+
 def _has_adapter_bank(model) -> bool:
     return any(m.__dict__.get("_qz_adapter_bank") is not None for m in model.modules())
 
@@ -755,13 +767,18 @@ class StreamSession:
     constraint / logit_bias_slots: DecodeSession's, per stream: prefill(), admit() and extend() take
     constraint_start (admit under a captured graph follows it without recapture; extend's None keeps the
     state, and the appended tokens do not advance it), fork(src, dst) copies the state, and a stream
-    that is not live keeps its state."""
+    that is not live keeps its state.
+
+    decode_rows (None: everything as it was): 17..64 calls integration.set_decode_rows(model, decode_rows),
+    so a step of up to that many rows reads every 4-bit weight once on the wide multi-token kernel
+    instead of taking the prefill route; a row's bits are those of the 2..16-row step."""
 
     def __init__(self, model, batch: int, max_len: int, *, graph: bool = True, prefill_chunk: Optional[int] = None,
                  kv_pages: Optional[int] = None, prefix_cache: bool = False, kv_dtype: Optional[str] = None,
                  logprobs: Optional[int] = None, prompt_logprobs: bool = False, constraint=None,
-                 logit_bias_slots: int = 0):
+                 logit_bias_slots: int = 0, decode_rows: Optional[int] = None):
         _check_kv_dtype(kv_dtype, "StreamSession", kv_pages)
+        _set_decode_rows(model, decode_rows)
         _check_logprobs(logprobs, "StreamSession")
         if prompt_logprobs and prefill_chunk is None:
             raise ValueError("StreamSession: prompt_logprobs needs prefill_chunk (the prompt's rows are scored "
@@ -1249,7 +1266,8 @@ class SpeculativeSession(StreamSession):
     prompt-lookup drafter layer_ops.ngram_draft over the stream's own history with suffixes of up to
     `ngram` tokens.  A subclass may replace it with anything that runs on the device and writes token
     ids of the vocabulary for every stream, live or not (the embedding looks all B T rows up).
-    batch * T is at most core.MT_MAX_TOKENS (the multi-token 4-bit kernel's rows).
+    batch * T is at most core.MT_MAX_TOKENS (the multi-token 4-bit kernel's rows), or with
+    decode_rows=17..64 at most that (the wide multi-token kernel; T itself at most layer_ops.VERIFY_MAX_T).
 
     sample=True: set_sampling() and seed() as in StreamSession, and a step draws every row with the
     uniform number of the position it sits at (layer_ops.verify_sample_step_streams): row i of stream
@@ -1269,7 +1287,8 @@ class SpeculativeSession(StreamSession):
     def __init__(self, model, batch: int, max_len: int, *, draft_tokens: int = 3, ngram: int = 3, graph: bool = True,
                  sample: bool = False, prefill_chunk: Optional[int] = None, kv_pages: Optional[int] = None,
                  prefix_cache: bool = False, kv_dtype: Optional[str] = None, logprobs: Optional[int] = None,
-                 prompt_logprobs: bool = False, constraint=None, logit_bias_slots: int = 0):
+                 prompt_logprobs: bool = False, constraint=None, logit_bias_slots: int = 0,
+                 decode_rows: Optional[int] = None):
         from .core import MT_MAX_TOKENS
 
         if int(draft_tokens) < 1:
@@ -1277,12 +1296,15 @@ class SpeculativeSession(StreamSession):
         if not 1 <= int(ngram) <= _ops.NGRAM_MAX:
             raise ValueError(f"SpeculativeSession: ngram must be in 1..{_ops.NGRAM_MAX}")
         T = int(draft_tokens) + 1
-        if batch * T > MT_MAX_TOKENS:
+        most = MT_MAX_TOKENS if decode_rows is None else int(decode_rows)
+        if batch * T > most or T > _ops.VERIFY_MAX_T:
             raise ValueError(f"SpeculativeSession: batch * (draft_tokens + 1) = {batch * T} rows per step, the "
-                             f"multi-token kernels take {MT_MAX_TOKENS}")
+                             f"multi-token kernels take {most} (decode_rows raises it to 64), and a stream's "
+                             f"window at most {_ops.VERIFY_MAX_T}")
         super().__init__(model, batch, max_len, graph=graph, prefill_chunk=prefill_chunk, kv_pages=kv_pages,
                          prefix_cache=prefix_cache, kv_dtype=kv_dtype, logprobs=logprobs,
-                         prompt_logprobs=prompt_logprobs, constraint=constraint, logit_bias_slots=logit_bias_slots)
+                         prompt_logprobs=prompt_logprobs, constraint=constraint, logit_bias_slots=logit_bias_slots,
+                         decode_rows=decode_rows)
         dev = self.device
         self.T, self.ngram, self.sample = T, int(ngram), bool(sample)
         self.tok = torch.zeros((batch, T), dtype=torch.int64, device=dev)
@@ -1357,7 +1379,7 @@ def _speculative_session(model, batch: int, max_len: int, prompt_lookup_num_toke
                          do_sample: bool, graph: bool, who: str, sampling: bool = False,
                          prefill_chunk: Optional[int] = None, kv_pages: Optional[int] = None,
                          kv_dtype: Optional[str] = None, logprobs: Optional[int] = None, constraint=None,
-                         logit_bias_slots: int = 0) -> SpeculativeSession:
+                         logit_bias_slots: int = 0, decode_rows: Optional[int] = None) -> SpeculativeSession:
     if do_sample and not sampling:
         raise ValueError(f"{who}: prompt_lookup_num_tokens verifies drafts against the greedy token; "
                          "do_sample is not supported with it unless prompt_lookup_sampling=True")
@@ -1365,7 +1387,7 @@ def _speculative_session(model, batch: int, max_len: int, prompt_lookup_num_toke
     return SpeculativeSession(model, batch, max_len, draft_tokens=int(prompt_lookup_num_tokens), ngram=n, graph=graph,
                               sample=bool(do_sample and sampling), prefill_chunk=prefill_chunk, kv_pages=kv_pages,
                               kv_dtype=kv_dtype, logprobs=logprobs, constraint=constraint,
-                              logit_bias_slots=logit_bias_slots)
+                              logit_bias_slots=logit_bias_slots, decode_rows=decode_rows)
 
 
 def _run_speculative(sess: SpeculativeSession, max_new_tokens: int) -> None:
@@ -1378,7 +1400,8 @@ def _run_speculative(sess: SpeculativeSession, max_new_tokens: int) -> None:
 
 def _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attention_mask, graph,
                           prompt_lookup_num_tokens, max_matching_ngram_size, sampling=None,
-                          penalties=None, logprobs=None, constraint=None, constraint_start=None, bias=None):
+                          penalties=None, logprobs=None, constraint=None, constraint_start=None, bias=None,
+                          decode_rows=None):
     """generate()'s result from a SpeculativeSession: every stream runs to its EOS or to max_new_tokens,
     then the rows are laid out as the plain loop leaves them -- S + n columns, n the first multiple of
     STOP_CHECK_EVERY by which every stream had its EOS (max_new_tokens if there is none), each
@@ -1390,7 +1413,8 @@ def _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attent
     sess = _speculative_session(model, B, S + max_new_tokens, prompt_lookup_num_tokens, max_matching_ngram_size,
                                 sampling is not None, graph, "generate", sampling is not None, logprobs=logprobs,
                                 constraint=constraint,
-                                logit_bias_slots=max((len(d) for d in bias), default=0) if bias is not None else 0)
+                                logit_bias_slots=max((len(d) for d in bias), default=0) if bias is not None else 0,
+                                decode_rows=decode_rows)
     _open_constraints(sess, bias)
     if sampling is not None:
         sess.set_sampling(temperature=sampling["temperature"], top_k=sampling["top_k"], top_p=sampling["top_p"])
@@ -1424,7 +1448,8 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
                     repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
                     no_repeat_ngram_size=None, min_new_tokens=None, prefill_chunk: Optional[int] = None,
                     kv_pages: Optional[int] = None, kv_dtype: Optional[str] = None, logprobs: Optional[int] = None,
-                    constraint=None, constraint_start=None, logit_bias=None, suppress_tokens=None):
+                    constraint=None, constraint_start=None, logit_bias=None, suppress_tokens=None,
+                    decode_rows: Optional[int] = None):
     """generate() for prompts of different lengths: `prompts` are 1-D int64 tensors; returns one 1-D
     int64 tensor per prompt on the model's device, the prompt followed by up to max_new_tokens picked
     tokens of its own, ending with eos_token_id if the stream picked it.  A stream that stopped writes
@@ -1444,7 +1469,8 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     logprobs: as generate() takes it; the GenerateOutput's fields are lists with one tensor per prompt,
     each cut to that prompt's sequence.
     constraint, constraint_start, logit_bias, suppress_tokens: as generate() takes them, one value or one
-    per prompt."""
+    per prompt.
+    decode_rows: as generate() takes it."""
     _check_logprobs(logprobs, "generate_ragged")
     prompts = list(prompts)
     if not prompts or any((not isinstance(p, torch.Tensor)) or p.dim() != 1 or p.numel() < 1 for p in prompts):
@@ -1460,13 +1486,14 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     if prompt_lookup_num_tokens is not None:
         sess = _speculative_session(model, B, Smax + max_new_tokens, prompt_lookup_num_tokens,
                                     max_matching_ngram_size, do_sample, graph, "generate_ragged",
-                                    prompt_lookup_sampling, prefill_chunk, kv_pages, kv_dtype, logprobs, constraint, slots)
+                                    prompt_lookup_sampling, prefill_chunk, kv_pages, kv_dtype, logprobs, constraint, slots,
+                                    decode_rows)
     elif max_matching_ngram_size is not None:
         raise ValueError("generate_ragged: max_matching_ngram_size needs prompt_lookup_num_tokens")
     else:
         sess = StreamSession(model, B, Smax + max_new_tokens, graph=graph, prefill_chunk=prefill_chunk,
                              kv_pages=kv_pages, kv_dtype=kv_dtype, logprobs=logprobs, constraint=constraint,
-                             logit_bias_slots=slots)
+                             logit_bias_slots=slots, decode_rows=decode_rows)
     _open_constraints(sess, bias)
     if do_sample:
         sess.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p)

@@ -134,6 +134,7 @@ def fuse_projection_groups(model: nn.Module, groups=DEFAULT_PROJECTION_GROUPS) -
             compute = _linear4bit_group_compute if isinstance(members[0], Linear4bit) else sharded_group_compute
             assert isinstance(members[0], (Linear4bit, RowShardedLinear4bit))
             g = DecodeGroup(members, compute)
+            g.decode_rows = getattr(members[0], "decode_rows", g.decode_rows)   # set_decode_rows ran first
             for m in members:
                 m.__dict__["_qz_group"] = g
             n += 1
@@ -146,6 +147,30 @@ def unfuse_projection_groups(model: nn.Module) -> None:
     unfuse_prenorm(model)
     for m in model.modules():
         m.__dict__.pop("_qz_group", None)
+
+
+def set_decode_rows(model: nn.Module, rows: int) -> int:
+    """Opt every Linear4bit of `model` and every DecodeGroup built over them into multi-token launches
+    of up to `rows` rows: core.MT_MAX_TOKENS (16, the default: every route as it is) ..
+    core.MT_WIDE_MAX_TOKENS (64).  Above 16, an input of 17..rows rows runs on the wide multi-token
+    kernel -- through a fused group as one grouped launch, through a lone layer as one launch -- in
+    place of the prefill route; layers with an adapter or a bank, fp32 activations, K % 256 != 0 and
+    inputs autograd follows keep their route.  A row's bits are those of the 2..16-row step.
+    Returns the number of layers set; set_decode_rows(model, 16) undoes it."""
+    from .core import MT_MAX_TOKENS, MT_WIDE_MAX_TOKENS
+
+    rows = int(rows)
+    if not MT_MAX_TOKENS <= rows <= MT_WIDE_MAX_TOKENS:
+        raise ValueError(f"set_decode_rows: rows must be in {MT_MAX_TOKENS}..{MT_WIDE_MAX_TOKENS}, got {rows}")
+    n = 0
+    for m in model.modules():
+        if isinstance(m, Linear4bit):
+            m.decode_rows = rows
+            grp = m.__dict__.get("_qz_group")
+            if grp is not None:
+                grp.decode_rows = rows
+            n += 1
+    return n
 
 
 def _identity(x):

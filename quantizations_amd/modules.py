@@ -25,7 +25,8 @@ import torch.nn as nn
 from . import _lib, lora
 from .autograd import MatMul4Bit
 from .core import (MT_MAX_TOKENS, Params4bit, QuantState, dequantize_4bit, exact_codes_for, gemm_4bit,
-                   gemm_4bit_grouped, gemv_4bit, gemv_4bit_grouped, gemv_4bit_pair_silu, grouped_tokens_ok)
+                   gemm_4bit_grouped, gemm_4bit_grouped_wide, gemm_4bit_wide, gemv_4bit, gemv_4bit_grouped,
+                   gemv_4bit_pair_silu, grouped_tokens_ok, grouped_wide_ok)
 
 
 def matmul_4bit(A: torch.Tensor, B: torch.Tensor, quant_state: QuantState, out: torch.Tensor = None, bias=None,
@@ -61,7 +62,13 @@ class DecodeGroup:
     pick theirs up if they are called with the SAME tensor object (identity +
     version check, so a new or modified input always recomputes).  Prefill
     inputs (more tokens) bypass the group.  Built by
-    ``integration.fuse_projection_groups``."""
+    ``integration.fuse_projection_groups``.
+
+    ``decode_rows`` (default MT_MAX_TOKENS; ``integration.set_decode_rows``) is the opt-in to the wide
+    multi-token launch: raised to 64, an input of 17..64 rows that the wide kernel takes runs as one
+    grouped wide launch (core.gemm_4bit_grouped_wide) instead of bypassing the group."""
+
+    decode_rows = MT_MAX_TOKENS
 
     def __init__(self, members, compute):
         self.members = list(members)
@@ -80,6 +87,20 @@ class DecodeGroup:
             return False
         k = x.shape[-1]
         return k > 0 and 1 <= x.numel() // k <= MT_MAX_TOKENS
+
+    def accepts_wide(self, x: torch.Tensor) -> bool:
+        """MT_MAX_TOKENS < rows <= decode_rows and the grouped wide launch takes every member: no
+        autograd, no adapter or bank, 16-bit CUDA input, K % 256 == 0.  Anything else keeps the
+        route it has without decode_rows."""
+        k = x.shape[-1]
+        if not (k > 0 and MT_MAX_TOKENS < x.numel() // k <= self.decode_rows) or grad_route(x):
+            return False
+        if self._compute is not _linear4bit_group_compute or not x.is_cuda:
+            return False
+        if any(m.adapter is not None or m.adapter_bank is not None or m.weight.quant_state is None
+               for m in self.members):
+            return False
+        return grouped_wide_ok(self.members[0]._input(x), [(m.weight, m.weight.quant_state) for m in self.members])
 
     @staticmethod
     def _version(x: torch.Tensor) -> int:
@@ -144,6 +165,9 @@ def _linear4bit_group_compute(group: DecodeGroup, x: torch.Tensor):
                   lora.bank_rows(first, xin)[1])
             banks = [None if f is not None else b for b, f in zip(banks, fused)]
         outs = gemm_4bit_grouped(xin, items, lora=lo)
+    elif not has_ad and all(b is None for b in banks) and grouped_wide_ok(xin, items) \
+            and xin.numel() // xin.shape[-1] <= group.decode_rows:
+        outs = gemm_4bit_grouped_wide(xin, items)    # 17..decode_rows rows (accepts_wide let them in)
     else:  # shapes the multi-token kernel does not take: each member as it would run alone
         outs = [matmul_4bit(xin, w, bias=b, quant_state=st, exact_codes=exact_codes_for(m0.compute_dtype))
                 for w, st, b in items]
@@ -192,6 +216,10 @@ class Linear4bit(nn.Linear):
         self.compute_type_is_set = False
         self.quant_state = None
         self.quant_storage = quant_storage
+
+    # Most rows this layer sends to a multi-token launch.  The default keeps every route as it is;
+    # integration.set_decode_rows(model, 64) opts 17..64-row inputs into the wide launch.
+    decode_rows = MT_MAX_TOKENS
 
     # -- LoRA adapter (lora.py): not a parameter or buffer, so not part of state_dict(); kept by
     # copy.deepcopy (it lives in __dict__) --
@@ -273,7 +301,7 @@ class Linear4bit(nn.Linear):
         if qs is None:
             raise RuntimeError("Linear4bit weight is not quantised yet: move the module to a GPU first")
         group = self.__dict__.get("_qz_group")
-        if group is not None and group.accepts(x):
+        if group is not None and (group.accepts(x) or group.accepts_wide(x)):
             return group.take(self, x)
         if group is not None and group.prenorm is not None:
             x = group.prenorm[2](x)      # prefill through a group that absorbed its RMSNorm
@@ -303,6 +331,9 @@ class Linear4bit(nn.Linear):
                 t, offs = lora.shrink_mt(xin, [bank])
                 out = gemm_4bit_grouped(xin, items, lora=(t, [(bank.B, offs[0])], bank.slots, tps))[0]
                 return _as_dtype(out, inp_dtype)
+        if ad is None and bank is None and self.decode_rows > MT_MAX_TOKENS and xin.shape[-1] > 0 and \
+                xin.numel() // xin.shape[-1] <= self.decode_rows and grouped_wide_ok(xin, [(self.weight, qs)]):
+            return _as_dtype(gemm_4bit_wide(xin, self.weight, qs, bias=bias), inp_dtype)   # 17..decode_rows rows
         out = matmul_4bit(xin, self.weight, bias=bias, quant_state=qs,
                           exact_codes=exact_codes_for(self.compute_dtype))
         if ad is not None:

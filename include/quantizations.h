@@ -419,6 +419,38 @@ int qz_prefill_attention(int dtype, int B, int T, int Hq, int Hkv, int D, int L,
                          const void *sin, long long cs_row, void *k_cache, void *v_cache, const long long *pos,
                          const long long *len, void *out, long long out_row, float scale, void *stream);
 
+/* Sliding-window attention over a ring KV cache (csrc/window_attn.hip): the two launches above for a
+ * model whose rows see only their last W keys (HF's sliding-window mask: key j is visible to a row at
+ * position p iff p - W < j <= p).
+ *   k_cache/v_cache [B, Hkv, R, D], contiguous, 16-B aligned: position p of stream b lives in slot p % R.
+ *   R is a positive multiple of 128 and R >= W + C - 1, C the most new tokens one launch writes per
+ *   stream (1 for the decode launch, T for the prefill launch); anything else is QZ_ERR_SHAPE, nothing
+ *   launched.  Positions are not bounded by R: a stream of any length runs in the same ring.  Slots
+ *   that were never written or hold positions outside a row's window may hold anything, NaN included.
+ * qz_decode_attention_window: qz_decode_attention_streams over the ring.  Stream b's new k/v go to slot
+ *   pos[b] % R; grid (R/128, Hq, B), a ring chunk that holds nothing visible is never loaded;
+ *   work (R > 128 only): B*Hkv*(R/128)*(Hq/Hkv)*(D+2) floats.  For pos[b] < min(W, R) out[b] and the
+ *   rows written are bit-identical to qz_decode_attention_streams on a cache of length R.  pos[b] < 0:
+ *   out[b] is NaN, nothing of stream b is written, other streams are unaffected.
+ * qz_prefill_attention_window: qz_prefill_attention over the ring.  Token row (b, i), i < len[b], sits at
+ *   position pos[b] + i; the launch writes all keys and values first, then attends over O(W + 64) keys
+ *   per 64-row query tile.  A row's output bits depend on its own q/cos/sin row, its position, W, cache
+ *   row b and where its query tile starts (pos[b] + 64*(i/64): the online softmax runs over 64-key tiles
+ *   from the absolute tile of that row's first visible key) -- not on T, len or the other streams.
+ *   Where pos[b] + len[b] <= W (nothing has aged out) the bits are qz_prefill_attention's.  pos[b] < 0
+ *   makes the len[b] real rows NaN and writes nothing; rows i >= len[b] are zeros.
+ * Every other operand, the alignment rules and the status codes are the flat launches'. */
+int qz_decode_attention_window(int dtype, int B, int Hq, int Hkv, int D, int R, int W, const void *q,
+                               long long q_row, const void *k, long long k_row, const void *v, long long v_row,
+                               const void *cos, const void *sin, long long cs_row, void *k_cache, void *v_cache,
+                               const long long *pos, void *out, long long out_row, float *work, float scale,
+                               void *stream);
+int qz_prefill_attention_window(int dtype, int B, int T, int Hq, int Hkv, int D, int R, int W, const void *q,
+                                long long q_row, const void *k, long long k_row, const void *v, long long v_row,
+                                const void *cos, const void *sin, long long cs_row, void *k_cache, void *v_cache,
+                                const long long *pos, const long long *len, void *out, long long out_row,
+                                float scale, void *stream);
+
 /* Paged KV cache (csrc/paged_attn.hip): the three launches above through a page table.
  *   A page holds qz_kv_page_size() = 128 positions (fixed: the decode head's key chunk, two of the
  *   prefill kernel's key tiles).  k_pool/v_pool [P, Hkv, 128, D], contiguous, 16-B aligned, one pair

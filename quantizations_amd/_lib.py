@@ -98,6 +98,10 @@ SIGNATURES = {
                                    _ll, _p, _f, _p],
     "qz_prefill_attention": [_i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p, _p, _p,
                              _ll, _f, _p],
+    "qz_decode_attention_window": [_i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p, _p,
+                                   _ll, _p, _f, _p],
+    "qz_prefill_attention_window": [_i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p,
+                                    _p, _p, _ll, _f, _p],
     "qz_kv_page_size": [],
     "qz_decode_attention_paged": [_i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p, _ll,
                                   _p, _p, _ll, _p, _f, _p],

@@ -318,10 +318,20 @@ template <int D> struct AttnLds {
 // are branch-free -- a lane past L reads row j0, a lane that rotates nothing reads a pair another
 // lane reads -- because hipcc counts a wait (vmcnt(N), loads behind it left in flight) only while no
 // branch stands between a load and its wait; behind a branch it drains every load (vmcnt(0)).
-template <int DT, int D, bool STREAMS, bool VERIFY, bool PAGED, bool KV8, bool SPEC>
+// RULE (STREAMS without VERIFY): where the stream's position lies in the body's key coordinates and which
+// keys it admits.  FlatKeys is the static cache -- slot = position, key j visible iff j <= p, a position at
+// or past L has no slot -- and compiles to the expressions it replaced.  RingKeys (window_attn.hip) is one
+// 128-slot chunk of a ring.
+struct FlatKeys {
+  __device__ __forceinline__ long long position(long long p) const { return p; }
+  __device__ __forceinline__ bool visible(long long j, long long p) const { return j <= p; }
+  __device__ __forceinline__ bool no_slot(long long p, int L) const { return p >= L; }
+};
+
+template <int DT, int D, bool STREAMS, bool VERIFY, bool PAGED, bool KV8, bool SPEC, class RULE = FlatKeys>
 __device__ __forceinline__ long long decode_attn_body(const DecodeAttnArgs &a, int split, int hq, int b,
                                                       const AttnLds<D> &S, int cb, long long pv, int page,
-                                                      unsigned long long *stamps) {
+                                                      unsigned long long *stamps, const RULE rule = RULE{}) {
   static_assert(STREAMS || !VERIFY, "the verify form computes its mask from the position");
   static_assert(STREAMS || !PAGED, "the paged form has a position per stream");
   static_assert(PAGED || !KV8, "kv8 rows live in page pools");
@@ -333,7 +343,7 @@ __device__ __forceinline__ long long decode_attn_body(const DecodeAttnArgs &a, i
   QZ_ATTN_STAMP_DECL;
   QZ_ATTN_STAMP(0);
   // p first: a uniform load in front of every asm statement stays a scalar load
-  const long long p = VERIFY ? pv : STREAMS ? a.pos[b] : *a.pos;
+  const long long p = VERIFY ? pv : STREAMS ? rule.position(a.pos[b]) : *a.pos;
   // the arguments the tail needs, read once and kept in SGPRs
   const float scale = keep_s(a.scale);
   void *const out = keep_sp(a.out);
@@ -379,7 +389,7 @@ __device__ __forceinline__ long long decode_attn_body(const DecodeAttnArgs &a, i
     s1b = raw(sb, ri); s2b = raw(sb, ri + H2);
   }
   unsigned char mk;
-  if constexpr (STREAMS) mk = (in_l && j <= p) ? (unsigned char)1 : (unsigned char)0;
+  if constexpr (STREAMS) mk = (in_l && rule.visible(j, p)) ? (unsigned char)1 : (unsigned char)0;
   else mk = a.mask[(long long)b * a.mb + (in_l ? j : 0) * a.mj];   // past L: key 0's byte, dropped below
   constexpr int NR = KV8 ? NW / 8 : NW / 4;   // 16-B loads of half a row
   u32x4 kr[NR], vr[NR];
@@ -585,7 +595,7 @@ __device__ __forceinline__ long long decode_attn_body(const DecodeAttnArgs &a, i
     for (int i = 0; i < 4 * NSUB; ++i) acc += s_pv[i * D + t];
     // a full cache (p >= L) has no slot for the new token: HF's StaticLayer.update fails on the
     // out-of-range index_copy_; here the output is NaN (never a silently stale attention)
-    if (p >= L) acc = __builtin_nanf("");
+    if (rule.no_slot(p, L)) acc = __builtin_nanf("");
     if (nsplit == 1) {
       char *ob = reinterpret_cast<char *>(out) + ((long long)b * os + (long long)hq * D) * ES;
       store_f32<DT>(ob, t, __fdiv_rn(acc, l));
@@ -612,12 +622,13 @@ __device__ __forceinline__ long long decode_attn_body(const DecodeAttnArgs &a, i
 }
 
 // The head: the body's form for the cache length, chosen once (uniform over the launch).
-template <int DT, int D, bool STREAMS = false, bool VERIFY = false, bool PAGED = false, bool KV8 = false>
+template <int DT, int D, bool STREAMS = false, bool VERIFY = false, bool PAGED = false, bool KV8 = false, class RULE = FlatKeys>
 __device__ __forceinline__ long long decode_attn_head(const DecodeAttnArgs &a, int split, int hq, int b,
                                                       const AttnLds<D> &S, int cb = 0, long long pv = 0,
-                                                      int page = 0, unsigned long long *stamps = nullptr) {
-  if (a.L <= kAttnSpecL) return decode_attn_body<DT, D, STREAMS, VERIFY, PAGED, KV8, true>(a, split, hq, b, S, cb, pv, page, stamps);
-  return decode_attn_body<DT, D, STREAMS, VERIFY, PAGED, KV8, false>(a, split, hq, b, S, cb, pv, page, stamps);
+                                                      int page = 0, unsigned long long *stamps = nullptr,
+                                                      const RULE rule = RULE{}) {
+  if (a.L <= kAttnSpecL) return decode_attn_body<DT, D, STREAMS, VERIFY, PAGED, KV8, true>(a, split, hq, b, S, cb, pv, page, stamps, rule);
+  return decode_attn_body<DT, D, STREAMS, VERIFY, PAGED, KV8, false>(a, split, hq, b, S, cb, pv, page, stamps, rule);
 }
 
 // The chunk of token row r that a per-stream kernel does not compute (its early exit, uniform over the

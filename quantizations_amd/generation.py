@@ -212,6 +212,7 @@ class DecodeSession:
 
         if batch < 1 or max_len < 1:
             raise ValueError("DecodeSession: batch and max_len must be positive")
+        _refuse_window(model, "DecodeSession", "the shared position and bool mask")
         _check_logprobs(logprobs, "DecodeSession")
         self.model, self.batch, self.max_len = model, int(batch), int(max_len)
         self.device = next(model.parameters()).device
@@ -595,6 +596,18 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, do_sample: 
     if constraint is None and constraint_start is not None:
         raise ValueError("generate: constraint_start needs constraint")
     slots = max((len(d) for d in bias), default=0) if bias is not None else 0
+    if _window_of(model, "generate") is not None:
+        # a sliding-window model: the StreamSession path (ring cache), equal-length prompts as ragged ones
+        if attention_mask is not None or logprobs is not None:
+            raise ValueError("generate: a sliding-window model runs in a StreamSession; call generate_ragged for "
+                             "padded prompts or logprobs")
+        seqs = generate_ragged(model, list(input_ids), max_new_tokens, do_sample=do_sample, temperature=temperature,
+                               top_k=top_k, top_p=top_p, generator=generator, eos_token_id=eos_token_id, graph=graph,
+                               prompt_lookup_num_tokens=prompt_lookup_num_tokens, constraint=constraint,
+                               constraint_start=constraint_start, logit_bias=logit_bias,
+                               suppress_tokens=suppress_tokens, decode_rows=decode_rows, **penalties)
+        fill = 0 if eos_token_id is None else int(eos_token_id)
+        return torch.nn.utils.rnn.pad_sequence(seqs, batch_first=True, padding_value=fill)
     if prompt_lookup_num_tokens is not None:
         sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator) if do_sample else None
         return _generate_speculative(model, input_ids, max_new_tokens, eos_token_id, attention_mask, graph,
@@ -706,6 +719,55 @@ class PagedKVCache:
                            "(_qz_paged); this forward took another path")
 
 
+class RingLayer:
+    """One layer of a RingKVCache: the K and V rings [B, Hkv, R, D] as keys / values."""
+
+    def __init__(self, keys: torch.Tensor, values: torch.Tensor):
+        self.keys, self.values = keys, values
+
+
+class RingKVCache:
+    """What a sliding-window session hands the decoder as past_key_values: per layer one K and one V ring
+    [B, Hkv, ring, D] in which position p of a stream lives in slot p % ring, for a model whose rows see
+    their last `window` positions.  ring = layer_ops.ring_size(window, chunk), `chunk` the most tokens one
+    launch writes per stream: the cache's size does not depend on how long the streams run.  Every layer
+    has the same geometry.  Like PagedKVCache it is read through .layers[i] by the fused attention
+    (_qz_window) only; anything that tried to use it as a transformers cache ends in update()."""
+
+    def __init__(self, config, batch: int, window: int, chunk: int, dtype, device):
+        head_dim = getattr(config, "head_dim", None) or config.hidden_size // config.num_attention_heads
+        self.window, self.ring = int(window), _ops.ring_size(int(window), int(chunk))
+        shape = (int(batch), config.num_key_value_heads, self.ring, head_dim)
+        self.layers = [RingLayer(torch.zeros(shape, dtype=dtype, device=device),
+                                 torch.zeros(shape, dtype=dtype, device=device))
+                       for _ in range(config.num_hidden_layers)]
+
+    def update(self, *args, **kwargs):
+        raise RuntimeError("RingKVCache: keys and values are written by the window attention launches "
+                           "(_qz_window); this forward took another path")
+
+
+def _window_of(model, who: str) -> Optional[int]:
+    """config.sliding_window where every layer slides (None: a full-attention model).  A model that mixes
+    full and sliding layers is refused: the ring has one geometry for all layers."""
+    cfg = model.config
+    W = getattr(cfg, "sliding_window", None)
+    kinds = set(getattr(cfg, "layer_types", None) or ())
+    if len(kinds) > 1:
+        raise ValueError(f"{who}: the model mixes layer types {sorted(kinds)}; per-layer local/global attention "
+                         "is not supported (one cache geometry serves every layer)")
+    if W is None or kinds == {"full_attention"}:
+        return None
+    return int(W)
+
+
+def _refuse_window(model, who: str, what: str) -> None:
+    if _window_of(model, who) is not None:
+        raise ValueError(f"{who}: {what} does not serve a sliding-window model (config.sliding_window="
+                         f"{model.config.sliding_window}); use StreamSession, whose ring cache and window "
+                         "attention launches do")
+
+
 def _set_decode_rows(model, decode_rows) -> None:
     """The sessions' and generate()'s decode_rows keyword: None leaves the model alone."""
     if decode_rows is not None:
@@ -794,6 +856,14 @@ class StreamSession:
                              "attention)")
         if prefix_cache and kv_pages is None:
             raise ValueError("StreamSession: prefix_cache shares pages; open the session with kv_pages")
+        self.window = _window_of(model, "StreamSession")
+        if self.window is not None:
+            if isinstance(self, SpeculativeSession):
+                _refuse_window(model, "SpeculativeSession", "the verify window")
+            if kv_pages is not None or kv_dtype is not None:
+                _refuse_window(model, "StreamSession", "kv_pages / kv_dtype (no paged or FP8 ring)")
+            if prefill_chunk is None:
+                prefill_chunk = WINDOW_PREFILL_CHUNK   # the ring is written by the window launches only
         self.prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
         self.device = _single_gpu_prepared(model, "StreamSession")
         from transformers.cache_utils import StaticCache
@@ -809,6 +879,12 @@ class StreamSession:
             self.cache = PagedKVCache(model.config, int(kv_pages), model.get_input_embeddings().weight.dtype, dev,
                                       kv_dtype=kv_dtype)
             self._extra = {"_qz_paged": (self.pages.table,)}
+        elif self.window is not None:
+            # max_len bounds positions (hist, the rotary table), not the cache.  At least 3 tokens of room: the
+            # capture's two warm-up steps and the captured one write slots pos .. pos + 2 before pos is put back
+            self.cache = RingKVCache(model.config, self.batch, self.window, max(self.prefill_chunk, 3),
+                                     model.get_input_embeddings().weight.dtype, dev)
+            self._extra = {"_qz_window": (self.window,)}
         else:
             self.cache = StaticCache(config=model.config, max_cache_len=self.max_len)
         self._scratch = None   # admit()'s batch-1 StaticCache, made on first use
@@ -881,8 +957,8 @@ class StreamSession:
 
     def _init_cache(self) -> None:
         """Chunk mode: lay the StaticCache out before the first window (nothing calls its update())."""
-        if self.pages is not None:
-            return   # the pools are there
+        if self.pages is not None or self.window is not None:
+            return   # the pools / rings are there
         cfg = self.model.config
         head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
         dtype = self.model.get_input_embeddings().weight.dtype
@@ -1246,6 +1322,7 @@ class StreamSession:
         return [self.hist[b, :p + 1].clone() for b, p in enumerate(pos)]
 
 
+WINDOW_PREFILL_CHUNK = 128    # a sliding-window session's prefill_chunk where none is given
 SPECULATIVE_CHECK_EVERY = 4   # speculative generate: steps between host looks at `live`
 PROMPT_LOOKUP_NGRAM = 2       # transformers' default max_matching_ngram_size
 

@@ -242,7 +242,7 @@ RMSNORM_CLASSES = ("LlamaRMSNorm", "MistralRMSNorm", "Qwen2RMSNorm")
 # MLPs whose forward is down_proj(act_fn(gate_proj(x)) * up_proj(x)) (modeling_llama.py:174-176)
 MLP_CLASSES = ("LlamaMLP", "MistralMLP", "Qwen2MLP")
 # decoder layers whose forward is exactly LlamaDecoderLayer's (modeling_llama.py:295-324)
-DECODER_CLASSES = ("LlamaDecoderLayer",)
+DECODER_CLASSES = ("LlamaDecoderLayer", "MistralDecoderLayer")
 # attention modules whose modeling module's apply_rotary_pos_emb is Llama's half-split
 # rotation (modeling_llama.py:138-160); others (e.g. Cohere's interleaved
 # rotate_half) keep their own code
@@ -359,7 +359,12 @@ def _fused_attention_forward(mod: nn.Module, orig):
     paged twin of that keyword's launch (layer_ops.decode_attention_paged, decode_attention_verify_paged,
     prefill_attention_paged; a prefill window's streams are rows row0 .. row0 + nb - 1 of the table)
     -- or raises.  Where the layer's pools are uint8 (PagedKVCache(kv_dtype="fp8"): kv8 blocks
-    [P, Hkv, 128 (D + 1)]) the layer runs the *_paged_kv8 launch of the same keyword instead."""
+    [P, Hkv, 128 (D + 1)]) the layer runs the *_paged_kv8 launch of the same keyword instead.
+
+    `_qz_window` = (W,) (generation.StreamSession on a model with config.sliding_window) goes beside
+    `_qz_stream_pos` or `_qz_prefill`: the cache's layer holds rings [B, Hkv, R, D] as keys / values
+    (generation.RingKVCache), position p lives in slot p % R and a row sees its last W positions.  The
+    layer runs layer_ops.decode_attention_window / prefill_attention_window -- or raises."""
     from . import layer_ops
     from .layer_ops import (decode_attention, decode_attention_streams, decode_attention_streams_supported,
                             decode_attention_supported, decode_attention_verify, decode_attention_verify_supported)
@@ -412,6 +417,42 @@ def _fused_attention_forward(mod: nn.Module, orig):
             out = verify_paged(q, k, v, cos, sin, keys, values, table, verify_pos, nq, mod.scaling)
         else:
             out = decode_paged(q, k, v, cos, sin, keys, values, table, stream_pos, nq, mod.scaling)
+        return _project(mod.o_proj, out, residual), None
+
+    def window_forward(hidden_states, position_embeddings, past_key_values, window, stream_pos, prefill, residual,
+                       kwargs):
+        if (stream_pos is not None) + (prefill is not None) != 1:
+            raise ValueError("_qz_window goes with exactly one of _qz_stream_pos and _qz_prefill")
+        W, = window
+        layers, idx = getattr(past_key_values, "layers", None), getattr(mod, "layer_idx", None)
+        layer = layers[idx] if layers is not None and idx is not None and idx < len(layers) else None
+        if (layer is None or type(layer).__name__ != "RingLayer" or hidden_states.dim() != 3
+                or position_embeddings is None or kwargs.get("output_attentions", False) or mod.training
+                or layer.keys.dim() != 4 or layer.keys.shape[-1] != mod.head_dim):
+            raise ValueError("_qz_window: the window launches need a RingKVCache layer of this module's head_dim")
+        keys, values = layer.keys, layer.values
+        cos, sin = position_embeddings
+        nq = keys.shape[1] * (mod.config.num_attention_heads // mod.config.num_key_value_heads)
+        if prefill is not None:
+            pos, length, row0 = prefill
+            nb = hidden_states.shape[0]
+            if not (isinstance(row0, int) and 0 <= row0 and row0 + nb <= keys.shape[0]):
+                raise ValueError("_qz_window: rows row0 .. row0 + nb - 1 are not rows of the ring")
+            keys, values = keys[row0:row0 + nb], values[row0:row0 + nb]
+            ok = layer_ops.prefill_attention_window_supported(hidden_states, cos, keys, values, pos, length, nq, W)
+        else:
+            ok = layer_ops.decode_attention_window_supported(hidden_states, cos, keys, values, stream_pos, nq, W)
+        if not ok:
+            raise ValueError("_qz_window: the window launch does not take these shapes/dtypes/layout/ring")
+        q = mod.q_proj(hidden_states)
+        k = mod.k_proj(hidden_states)
+        v = mod.v_proj(hidden_states)
+        if q.shape[-1] != nq * mod.head_dim or k.shape[-1] != keys.shape[1] * mod.head_dim:
+            raise ValueError("_qz_window: the projections' widths differ from the ring's heads")
+        if prefill is not None:
+            out = layer_ops.prefill_attention_window(q, k, v, cos, sin, keys, values, pos, length, nq, mod.scaling, W)
+        else:
+            out = layer_ops.decode_attention_window(q, k, v, cos, sin, keys, values, stream_pos, nq, mod.scaling, W)
         return _project(mod.o_proj, out, residual), None
 
     def prefill_forward(hidden_states, position_embeddings, past_key_values, spec, residual, kwargs):
@@ -481,8 +522,13 @@ def _fused_attention_forward(mod: nn.Module, orig):
 
     def forward(hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None,
                 _qz_residual=None, _qz_stream_pos=None, _qz_verify_pos=None, _qz_prefill=None, _qz_paged=None,
-                **kwargs):
+                _qz_window=None, **kwargs):
         # _qz_residual (the residual-fused decoder layer): return residual + attention output
+        if _qz_window is not None:
+            if _qz_paged is not None or _qz_verify_pos is not None:
+                raise ValueError("_qz_window excludes _qz_paged and _qz_verify_pos (no paged ring, no verify window)")
+            return window_forward(hidden_states, position_embeddings, past_key_values, _qz_window, _qz_stream_pos,
+                                  _qz_prefill, _qz_residual, kwargs)
         if _qz_paged is not None:
             return paged_forward(hidden_states, position_embeddings, past_key_values, _qz_paged, _qz_stream_pos,
                                  _qz_verify_pos, _qz_prefill, _qz_residual, kwargs)

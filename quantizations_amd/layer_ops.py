@@ -378,6 +378,95 @@ def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: to
     return out
 
 
+def ring_size(window: int, chunk: int = 1) -> int:
+    """Slots of a ring KV cache for a sliding window of `window` keys when one launch writes up to `chunk`
+    new tokens per stream: round_up(window + chunk - 1, 128).  The launch stores its keys before it
+    attends, so the chunk's last key must not land on the slot its first row still reads."""
+    if window < 1 or chunk < 1:
+        raise ValueError("ring_size: window and chunk must be at least 1")
+    return -(-(window + chunk - 1) // ATTN_CHUNK) * ATTN_CHUNK
+
+
+def _ring_ok(ring: int, window, chunk: int) -> bool:
+    return (isinstance(window, int) and not isinstance(window, bool) and window >= 1 and ring % ATTN_CHUNK == 0
+            and ring >= window + chunk - 1)
+
+
+def _check_ring(name: str, ring: int, window, chunk: int) -> None:
+    if not _ring_ok(ring, window, chunk):
+        raise ValueError(f"{name}: a ring of {ring} slots cannot serve window {window} with {chunk} new token(s) per "
+                         f"launch: it must be a multiple of {ATTN_CHUNK} and at least window + tokens - 1 "
+                         f"(layer_ops.ring_size)")
+
+
+def decode_attention_window_supported(q: torch.Tensor, cos: torch.Tensor, key_cache: torch.Tensor,
+                                      value_cache: torch.Tensor, pos, num_heads: int, window) -> bool:
+    """What qz_decode_attention_window takes: decode_attention_streams_supported's operands with the caches
+    as rings [B, Hkv, R, D], R a multiple of 128 and R >= window >= 1.  Metadata only."""
+    return (decode_attention_streams_supported(q, cos, key_cache, value_cache, pos, num_heads)
+            and _ring_ok(key_cache.shape[2], window, 1))
+
+
+def decode_attention_window(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                            key_cache: torch.Tensor, value_cache: torch.Tensor, pos: torch.Tensor, num_heads: int,
+                            scale: float, window: int) -> torch.Tensor:
+    """decode_attention_streams for a sliding window over a ring cache (qz_decode_attention_window): caches
+    [B, Hkv, R, D]; stream b's new k/v go to slot pos[b] % R and it sees positions
+    max(0, pos[b] - window + 1) .. pos[b].  Positions are not bounded by R.  For pos[b] < min(window, R) the
+    output and the rows written carry decode_attention_streams' bits on an R-long cache; pos[b] < 0 gives
+    that stream a NaN row and writes nothing of it.  Returns [B, 1, Hq*D]."""
+    if key_cache.dim() == 4:
+        _check_ring("decode_attention_window", key_cache.shape[2], window, 1)
+    if not decode_attention_window_supported(q, cos, key_cache, value_cache, pos, num_heads, window):
+        raise ValueError("decode_attention_window: unsupported shapes/dtypes/layout")
+    B, Hkv, R, D = key_cache.shape
+    q2, k2, v2, out, work, cs_row = _attention_launch_operands("decode_attention_window", q, k, v, cos, sin,
+                                                               key_cache, num_heads)
+    _lib.check(_lib.lib.qz_decode_attention_window(
+        _lib.dtype_code(q.dtype), B, num_heads, Hkv, D, R, window, q2.data_ptr(), q2.stride(0), k2.data_ptr(),
+        k2.stride(0), v2.data_ptr(), v2.stride(0), cos.data_ptr(), sin.data_ptr(), cs_row, key_cache.data_ptr(),
+        value_cache.data_ptr(), pos.data_ptr(), out.data_ptr(), num_heads * D,
+        work.data_ptr() if work is not None else None, float(scale), _lib.stream_of(q)),
+        "qz_decode_attention_window")
+    return out
+
+
+def prefill_attention_window_supported(q: torch.Tensor, cos: torch.Tensor, key_cache: torch.Tensor,
+                                       value_cache: torch.Tensor, pos, length, num_heads: int, window) -> bool:
+    """What qz_prefill_attention_window takes: prefill_attention_supported's operands with the caches as
+    rings [B, Hkv, R, D], R a multiple of 128 and R >= window + T - 1.  Metadata only."""
+    return (prefill_attention_supported(q, cos, key_cache, value_cache, pos, length, num_heads)
+            and _ring_ok(key_cache.shape[2], window, q.shape[1]))
+
+
+def prefill_attention_window(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                             key_cache: torch.Tensor, value_cache: torch.Tensor, pos: torch.Tensor,
+                             length: torch.Tensor, num_heads: int, scale: float, window: int) -> torch.Tensor:
+    """prefill_attention for a sliding window over a ring cache (qz_prefill_attention_window): token (b, i)
+    with i < length[b] sits at position pos[b] + i, its k/v go to slot (pos[b] + i) % R and it sees the
+    last `window` positions up to its own.  O(window + 64) keys per 64-row query tile, whatever the
+    position.  A row's bits depend on its q/cos/sin row, its position, the window, cache row b and where
+    its query tile starts; while pos[b] + length[b] <= window they are prefill_attention's.  Rows
+    i >= length[b] are zeros; pos[b] < 0 makes the stream's real rows NaN.  Returns [B, T, Hq*D]."""
+    if key_cache.dim() == 4 and q.dim() == 3:
+        _check_ring("prefill_attention_window", key_cache.shape[2], window, q.shape[1])
+    if not prefill_attention_window_supported(q, cos, key_cache, value_cache, pos, length, num_heads, window):
+        raise ValueError("prefill_attention_window: unsupported shapes/dtypes/layout")
+    B, Hkv, R, D = key_cache.shape
+    T = q.shape[1]
+    _check_window("prefill_attention_window", q, k, v, cos, sin, num_heads, D)
+    if k.shape[2] != Hkv * D or v.shape[2] != Hkv * D:
+        raise ValueError("prefill_attention_window: k/v width differs from the cache's heads")
+    q2, qs, k2, ks, v2, vs, c2, s2, cs = _prefill_rows(q, k, v, cos, sin, B, T, D)
+    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
+    _lib.check(_lib.lib.qz_prefill_attention_window(
+        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, R, window, q2.data_ptr(), qs, k2.data_ptr(), ks,
+        v2.data_ptr(), vs, c2.data_ptr(), s2.data_ptr(), cs, key_cache.data_ptr(), value_cache.data_ptr(),
+        pos.data_ptr(), length.data_ptr(), out.data_ptr(), num_heads * D, float(scale), _lib.stream_of(q)),
+        "qz_prefill_attention_window")
+    return out
+
+
 KV_PAGE = 128  # positions per page of the paged cache (qz_kv_page_size(): the decode head's key chunk)
 
 

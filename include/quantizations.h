@@ -888,6 +888,29 @@ int qz_moe_down_4bit(int T, int H, int I, int E, int top_k, const void *h, int d
                      long long block_base, const int *idx, const float *w, const void *residual, void *y, int ldy,
                      void *stream);
 
+/* qz_moe_gemv_pair_silu_4bit / qz_moe_gemv_down_4bit -- the two expert launches above for ONE token
+ * row (T = 1: x [H], idx [top_k], w [top_k], h [top_k, I], y [H], residual [H]), on the byte-table
+ * GEMV of qz_gemv_4bit_pair_silu / qz_gemv_4bit instead of the multi-token body: one workgroup column
+ * per routing slot streams whole rows of the chosen expert (pair); a wave owns output rows for every
+ * slot and walks the slots in ascending (expert, slot) order (down).  Same operands, same semantics,
+ * the same roundings after each dot product (16-bit projections, qz_silu_mul's epilogue, a rounded
+ * product and a rounded add per term, the residual's two roundings); a dot product itself is summed in
+ * the dense GEMV's order, so outputs agree with the qz_moe_* twins to fp32 summation error, not bit
+ * for bit.  An idx entry outside [0, E) gives a zero h row / adds nothing.  idx is read on the device
+ * only.  QZ_ERR_SHAPE (nothing launched; run the twin) unless: dtype F16 or BF16; K % 2048 == 0 for
+ * K = H (pair) and K = I (down); K % blocksize == 0, and with double quant blocksize2 a multiple of
+ * the 2048 / blocksize blocks of a K-step; block_base and the blocks of one expert multiples of that
+ * count; E <= 64, top_k <= 8; B, x / h, h / y 16-B aligned; one expert under 2^32 elements. */
+int qz_moe_gemv_pair_silu_4bit(int H, int I, int E, int top_k, const void *x, int dtype, const unsigned char *B,
+                               int quant_type, int blocksize, const float *absmax, const unsigned char *qabsmax,
+                               const float *absmax2, const float *code2, const float *offset, int blocksize2,
+                               long long block_base, const int *idx, void *h, void *stream);
+int qz_moe_gemv_down_4bit(int H, int I, int E, int top_k, const void *h, int dtype, const unsigned char *B,
+                          int quant_type, int blocksize, const float *absmax, const unsigned char *qabsmax,
+                          const float *absmax2, const float *code2, const float *offset, int blocksize2,
+                          long long block_base, const int *idx, const float *w, const void *residual, void *y,
+                          void *stream);
+
 /* Routed mixture-of-experts above 16 rows (prompts, prefill chunks, scoring, wide batches): four
  * entry points, route -> plan -> gate/up/SiLU -> down, none of which returns a value to the host.
  * 1 <= T <= 65536 rows and T * top_k <= 131072 routing entries per call (else QZ_ERR_SHAPE: the

@@ -126,6 +126,8 @@ SIGNATURES = {
     "qz_moe_route": [_i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p],
     "qz_moe_pair_silu_4bit": [_i, _i, _i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _ll, _p, _p, _p],
     "qz_moe_down_4bit": [_i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _ll, _p, _p, _p, _p, _i, _p],
+    "qz_moe_gemv_pair_silu_4bit": [_i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _ll, _p, _p, _p],
+    "qz_moe_gemv_down_4bit": [_i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _ll, _p, _p, _p, _p, _p],
     "qz_moe_route_rows": [_i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p],
     "qz_moe_plan": [_i, _i, _i, _p, _p, _p, _p],
     "qz_moe_gemm_pair_silu_4bit": [_i, _i, _i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _ll, _p, _p, _p,

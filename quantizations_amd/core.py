@@ -1033,6 +1033,51 @@ def moe_down(h: Tensor, B: Tensor, state: QuantState, idx: Tensor, w: Tensor, E:
 
 
 # ---------------------------------------------------------------------------
+# the two expert launches for ONE token row on the byte-table GEMV (csrc/moe_gemv.hip).  Each returns
+# None for more than one row and where the library answers QZ_ERR_SHAPE: the caller runs moe_pair_silu
+# / moe_down, which take every shape.  The same values to fp32 summation error, not the same bits.
+def moe_gemv_pair_silu(x: Tensor, B: Tensor, state: QuantState, idx: Tensor, E: int) -> Optional[Tensor]:
+    """moe_pair_silu's h [1, top_k, I] for one row x [1, H] (qz_moe_gemv_pair_silu_4bit)."""
+    H = x.shape[-1]
+    if x.dtype not in (torch.float16, torch.bfloat16) or x.numel() != H:
+        return None
+    rows = _moe_weight(B, state, E, H, "moe_gemv_pair_silu")
+    x2 = _moe_rows(x, H)
+    top_k = _moe_routing(idx, None, 1, x.device, "moe_gemv_pair_silu")
+    h = torch.empty((1, top_k, rows // 2), dtype=x.dtype, device=x.device)
+    rc = lib.qz_moe_gemv_pair_silu_4bit(H, rows // 2, E, top_k, ptr(x2), dtype_code(x.dtype), ptr(B),
+                                        _lib.QUANT_TYPES[state.quant_type], state.blocksize, *state.scale_args(), 0,
+                                        ptr(idx), ptr(h), _lib.stream_of(x))
+    if rc == _lib.QZ_ERR_SHAPE:
+        return None
+    check(rc, "moe_gemv_pair_silu")
+    return h
+
+
+def moe_gemv_down(h: Tensor, B: Tensor, state: QuantState, idx: Tensor, w: Tensor, E: int,
+                  residual: Optional[Tensor] = None) -> Optional[Tensor]:
+    """moe_down's y [1, H] (+ residual) for one row's h [1, top_k, I] (qz_moe_gemv_down_4bit)."""
+    if h.dim() != 3 or h.shape[0] != 1 or h.dtype not in (torch.float16, torch.bfloat16) or not h.is_contiguous():
+        return None
+    I = h.shape[2]
+    H = _moe_weight(B, state, E, I, "moe_gemv_down")
+    top_k = _moe_routing(idx, w, 1, h.device, "moe_gemv_down")
+    if top_k != h.shape[1]:
+        raise ValueError("moe_gemv_down: h must be [1, top_k, I] for idx [1, top_k]")
+    if residual is not None and (residual.dtype != h.dtype or residual.numel() != H or
+                                 not residual.is_contiguous() or residual.device != h.device):
+        raise ValueError(f"moe_gemv_down: residual must be a contiguous {h.dtype} tensor of {H} elements")
+    y = torch.empty((1, H), dtype=h.dtype, device=h.device)
+    rc = lib.qz_moe_gemv_down_4bit(H, I, E, top_k, ptr(h), dtype_code(h.dtype), ptr(B),
+                                   _lib.QUANT_TYPES[state.quant_type], state.blocksize, *state.scale_args(), 0,
+                                   ptr(idx), ptr(w), ptr(residual), ptr(y), _lib.stream_of(h))
+    if rc == _lib.QZ_ERR_SHAPE:
+        return None
+    check(rc, "moe_gemv_down")
+    return y
+
+
+# ---------------------------------------------------------------------------
 # routed mixture-of-experts above 16 rows (csrc/moe_prefill.hip): route -> plan -> the two
 # expert-grouped tile GEMMs.  Nothing comes back to the host, so the chain can be captured.  Each
 # binding returns None where the library answers QZ_ERR_SHAPE, as its decode twin does.

@@ -69,12 +69,17 @@ MOE_BLOCK_CLASSES = ("MixtralSparseMoeBlock",)
 
 
 def replace_moe_blocks(model: nn.Module, quant_type: str = "nf4", compress_statistics: bool = True,
-                       blocksize: int = 64) -> nn.Module:
+                       blocksize: int = 64, decode_route: str = "mma") -> nn.Module:
     """Replace every mixture-of-experts block (MOE_BLOCK_CLASSES, matched by class name) with a
     moe.SparseMoe4bit built from its parameters: the stacked expert weights, which
     replace_with_bnb_linear does not see (they are nn.Parameters, not nn.Linear children), become
-    4-bit; the router stays dense.  The weights must be on a GPU.  Returns the model."""
+    4-bit; the router stays dense.  The weights must be on a GPU.  `decode_route` ("mma" or "gemv") is
+    set on the blocks created: SparseMoe4bit.decode_route, the expert launches of a one-row input.
+    Returns the model."""
     from .moe import SparseMoe4bit
+
+    if decode_route not in ("mma", "gemv"):
+        raise ValueError(f"replace_moe_blocks: decode_route must be 'mma' or 'gemv', not {decode_route!r}")
 
     for parent in list(model.modules()):
         for name, child in list(parent.named_children()):
@@ -83,6 +88,7 @@ def replace_moe_blocks(model: nn.Module, quant_type: str = "nf4", compress_stati
             parent._modules[name] = SparseMoe4bit(child.gate.weight.data, child.experts.gate_up_proj.data,
                                                   child.experts.down_proj.data, child.top_k, quant_type=quant_type,
                                                   compress_statistics=compress_statistics, blocksize=blocksize)
+            parent._modules[name].decode_route = decode_route
     return model
 
 
@@ -238,15 +244,16 @@ def unfuse_prenorm(model: nn.Module) -> None:
 # ---------------------------------------------------------------------------
 
 # norms whose forward is exactly LlamaRMSNorm's (modeling_llama.py:62-67)
-RMSNORM_CLASSES = ("LlamaRMSNorm", "MistralRMSNorm", "Qwen2RMSNorm")
+RMSNORM_CLASSES = ("LlamaRMSNorm", "MistralRMSNorm", "MixtralRMSNorm", "Qwen2RMSNorm")
 # MLPs whose forward is down_proj(act_fn(gate_proj(x)) * up_proj(x)) (modeling_llama.py:174-176)
 MLP_CLASSES = ("LlamaMLP", "MistralMLP", "Qwen2MLP")
-# decoder layers whose forward is exactly LlamaDecoderLayer's (modeling_llama.py:295-324)
-DECODER_CLASSES = ("LlamaDecoderLayer", "MistralDecoderLayer")
+# decoder layers whose forward is exactly LlamaDecoderLayer's (modeling_llama.py:295-324); Mixtral's is
+# that forward with a MixtralSparseMoeBlock as self.mlp
+DECODER_CLASSES = ("LlamaDecoderLayer", "MistralDecoderLayer", "MixtralDecoderLayer")
 # attention modules whose modeling module's apply_rotary_pos_emb is Llama's half-split
 # rotation (modeling_llama.py:138-160); others (e.g. Cohere's interleaved
 # rotate_half) keep their own code
-ATTENTION_CLASSES = ("LlamaAttention", "MistralAttention", "Qwen2Attention")
+ATTENTION_CLASSES = ("LlamaAttention", "MistralAttention", "MixtralAttention", "Qwen2Attention")
 _ROPE_PATCHED = {}  # module name -> original apply_rotary_pos_emb
 
 
@@ -664,10 +671,14 @@ def fuse_layer_ops(model: nn.Module, norm: bool = True, rope: bool = True, mlp: 
                 mod.apply_rotary_pos_emb = _fused_rope(fn)
                 n += 1
     if residual and attention and mlp and not decoder:
+        from .moe import SparseMoe4bit
+
         for m in model.modules():
+            # a SparseMoe4bit as the layer's mlp takes `_qz_residual` itself (its down launch adds it)
             if type(m).__name__ in DECODER_CLASSES and "forward" not in m.__dict__ and \
                     "_qz_fused_attn" in getattr(m, "self_attn", nn.Module()).__dict__ and \
-                    "_qz_fused_mlp" in getattr(m, "mlp", nn.Module()).__dict__:
+                    ("_qz_fused_mlp" in getattr(m, "mlp", nn.Module()).__dict__ or
+                     isinstance(getattr(m, "mlp", None), SparseMoe4bit)):
                 m.__dict__["forward"] = _residual_decoder_forward(m)
                 m.__dict__["_qz_residual_decoder"] = True
                 n += 1
@@ -697,8 +708,8 @@ def unfuse_layer_ops(model: nn.Module) -> None:
 # costs a decode step (profiles/r5_decode_anatomy_8b.txt), with the same values
 # ---------------------------------------------------------------------------
 
-ROTARY_CLASSES = ("LlamaRotaryEmbedding", "MistralRotaryEmbedding", "Qwen2RotaryEmbedding")
-MODEL_CLASSES = ("LlamaModel", "MistralModel", "Qwen2Model")
+ROTARY_CLASSES = ("LlamaRotaryEmbedding", "MistralRotaryEmbedding", "MixtralRotaryEmbedding", "Qwen2RotaryEmbedding")
+MODEL_CLASSES = ("LlamaModel", "MistralModel", "MixtralModel", "Qwen2Model")
 _MASK_PATCHED = {}  # modeling module name -> original create_causal_mask
 _ROPE_TABLE_MAX = 1 << 17
 

@@ -10,7 +10,9 @@ Dispatch: up to 16 rows of fp16 / bf16 on the GPU run three launches -- route, g
 hit experts, down projection with the weighted sum (csrc/moe.hip); more rows (prompts, prefill
 chunks, scoring passes, wide batches) run route, a device-side plan that sorts the routing entries by
 expert, and two expert-grouped tile GEMMs (csrc/moe_prefill.hip).  Both keep the expert choice in
-device memory, so the block never synchronises and can be captured in a graph.  Anything else (fp32,
+device memory, so the block never synchronises and can be captured in a graph.  ``decode_route = "gemv"``
+(opt-in) sends a one-row input's two expert launches to the byte-table GEMV form (csrc/moe_gemv.hip) where it
+takes the shape.  Anything else (fp32,
 shapes off the kernels' grid, ``prefill_route = "composed"``) runs the composed form with the same
 semantics: the host loop over hit experts, each dequantised on its row range and applied with
 ``F.linear``.  Inference only: an input that requires grad raises.
@@ -22,7 +24,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .core import (MOE_MAX_ENTRIES, MOE_MAX_ROWS, MT_MAX_TOKENS, Params4bit, QuantState, dequantize_4bit, moe_down,
-                   moe_gemm_down, moe_gemm_pair_silu, moe_pair_silu, moe_plan, moe_route, moe_route_rows)
+                   moe_gemm_down, moe_gemm_pair_silu, moe_gemv_down, moe_gemv_pair_silu, moe_pair_silu, moe_plan,
+                   moe_route, moe_route_rows)
 from .modules import grad_route
 
 
@@ -81,8 +84,14 @@ class SparseMoe4bit(nn.Module):
     # inputs of more than 16 rows: "auto" = the grouped tile GEMMs where they take the shape,
     # "composed" = always the host loop (kept reachable for timing and comparison)
     prefill_route = "auto"
+    # a one-row input: "mma" = the three launches every 1..16-row input takes (a row's bits do not depend
+    # on the batch), "gemv" = the expert launches on the byte-table GEMV (csrc/moe_gemv.hip: the same
+    # values to fp32 summation error, other bits) where they take the shape, else "mma"'s
+    decode_route = "mma"
 
-    def forward(self, hidden_states: torch.Tensor) -> torch.Tensor:
+    def forward(self, hidden_states: torch.Tensor, _qz_residual=None) -> torch.Tensor:
+        """`_qz_residual` (the residual-fused decoder layer): returns residual + block output, the add
+        inside the down launch where that launch takes one."""
         if grad_route(hidden_states):
             raise RuntimeError("SparseMoe4bit is inference-only: the input requires grad")
         if self.gate_up_proj.quant_state is None or self.down_proj.quant_state is None:
@@ -91,28 +100,42 @@ class SparseMoe4bit(nn.Module):
         y = None
         if self.prefill_route not in ("auto", "composed"):
             raise ValueError(f"SparseMoe4bit.prefill_route must be 'auto' or 'composed', not {self.prefill_route!r}")
+        if self.decode_route not in ("mma", "gemv"):
+            raise ValueError(f"SparseMoe4bit.decode_route must be 'mma' or 'gemv', not {self.decode_route!r}")
+        res = None
+        if _qz_residual is not None:
+            res = _qz_residual.reshape(x.shape)
+            res = res if res.is_contiguous() and res.dtype == x.dtype else None
+        added = res is not None
         if x.is_cuda and x.shape[0] >= 1 and x.dtype in (torch.float16, torch.bfloat16):
             if x.shape[0] <= MT_MAX_TOKENS:
-                y = self._routed(x)
+                y = self._routed(x, res)
             elif self.prefill_route == "auto":
-                y = self._grouped(x)
+                y = self._grouped(x, res)
         if y is None:
-            y = self._composed(x)
-        return y.reshape(hidden_states.shape)
+            y, added = self._composed(x), False
+        y = y.reshape(hidden_states.shape)
+        return y if _qz_residual is None or added else _qz_residual + y
 
-    def _routed(self, x):
+    def _routed(self, x, residual=None):
         """The three launches; None where one of them declines the shape."""
         E = self.num_experts
         r = moe_route(x, self.gate.weight, self.top_k)
         if r is None:
             return None
         idx, w = r
+        if self.decode_route == "gemv" and x.shape[0] == 1:
+            h = moe_gemv_pair_silu(x, self.gate_up_proj, self.gate_up_proj.quant_state, idx, E)
+            y = None if h is None else moe_gemv_down(h, self.down_proj, self.down_proj.quant_state, idx, w, E,
+                                                     residual)
+            if y is not None:
+                return y
         h = moe_pair_silu(x, self.gate_up_proj, self.gate_up_proj.quant_state, idx, E)
         if h is None:
             return None
-        return moe_down(h, self.down_proj, self.down_proj.quant_state, idx, w, E)
+        return moe_down(h, self.down_proj, self.down_proj.quant_state, idx, w, E, residual)
 
-    def _grouped(self, x):
+    def _grouped(self, x, residual=None):
         """More than 16 rows: route_rows, plan and the two grouped tile GEMMs, in row chunks of what one
         plan takes (a row has the same bits in any chunk); None where a launch declines the shape."""
         E = self.num_experts
@@ -133,7 +156,8 @@ class SparseMoe4bit(nn.Module):
             if y is None:
                 return None
             out.append(y)
-        return out[0] if len(out) == 1 else torch.cat(out)
+        y = out[0] if len(out) == 1 else torch.cat(out)
+        return y if residual is None else residual + y
 
     def _composed(self, x):
         """The same semantics from torch ops: MixtralTopKRouter, then the host loop over hit experts with

@@ -419,6 +419,30 @@ int qz_prefill_attention(int dtype, int B, int T, int Hq, int Hkv, int D, int L,
                          const void *sin, long long cs_row, void *k_cache, void *v_cache, const long long *pos,
                          const long long *len, void *out, long long out_row, float scale, void *stream);
 
+/* Group-tiled attention (csrc/attn_group.hip): qz_prefill_attention's window of up to T >= 1 new tokens
+ * per stream with every query head of a kv head in one MFMA tile, split over keys.  The rows of a
+ * 64-row tile are the (token, head-in-group) pairs r = i*(Hq/Hkv) + g of one kv head, token-major, so
+ * K and V are read once per tile whatever Hq/Hkv is and 1 <= Hq/Hkv <= 64 is served.  A workgroup
+ * takes one (row tile, key chunk, kv head, stream): the absolute keys [c*key_chunk, (c+1)*key_chunk)
+ * in tiles of 64; with more than one chunk it leaves fp32 partials in `work` that a combine launch
+ * merges in ascending chunk order.
+ *   key_chunk: a positive multiple of 64 (QZ_ERR_SHAPE otherwise).  key_chunk >= L: one pass, `work`
+ *     unused (may be NULL).  Otherwise ceil(L/key_chunk) chunks.
+ *   work: qz_attention_group_work_floats(...) floats, 16-B aligned: B*T*Hq*ceil(L/key_chunk)*(D+4),
+ *     0 when key_chunk >= L.  The size query returns 0 for a shape the launch refuses.
+ * Operands, the cache write (the bits every other launch stores), the validity rules (len, bad pos, rows
+ * past L, NaN above the last written position) and the alignment rules are qz_prefill_attention's.  The
+ * arithmetic inside a chunk is qz_prefill_attention's.  A row's output bits depend on its own
+ * q/cos/sin row, its position, cache row b and key_chunk (every key_chunk >= L gives the same bits) --
+ * not on T, the other streams or len.  Two launches, three with more than one chunk.  F16/BF16, D in
+ * {64, 128}, B, Hq <= 65535; status codes as qz_prefill_attention, nothing launched on an error. */
+long long qz_attention_group_work_floats(int B, int T, int Hq, int Hkv, int D, int L, int key_chunk);
+int qz_attention_group(int dtype, int B, int T, int Hq, int Hkv, int D, int L, int key_chunk, const void *q,
+                       long long q_row, const void *k, long long k_row, const void *v, long long v_row,
+                       const void *cos, const void *sin, long long cs_row, void *k_cache, void *v_cache,
+                       const long long *pos, const long long *len, void *out, long long out_row, float *work,
+                       float scale, void *stream);
+
 /* Sliding-window attention over a ring KV cache (csrc/window_attn.hip): the two launches above for a
  * model whose rows see only their last W keys (HF's sliding-window mask: key j is visible to a row at
  * position p iff p - W < j <= p).

@@ -98,6 +98,9 @@ SIGNATURES = {
                                    _ll, _p, _f, _p],
     "qz_prefill_attention": [_i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p, _p, _p,
                              _ll, _f, _p],
+    "qz_attention_group_work_floats": [_i, _i, _i, _i, _i, _i, _i],
+    "qz_attention_group": [_i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p, _p, _p,
+                           _ll, _p, _f, _p],
     "qz_decode_attention_window": [_i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p, _p,
                                    _ll, _p, _f, _p],
     "qz_prefill_attention_window": [_i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p, _p, _ll, _p, _p, _p,
@@ -184,7 +187,7 @@ RESTYPES = {"qz_absmax_mean_workspace": _ll, "qz_gemm_4bit_workspace_size": _ll,
             "qz_exchange_bytes": _ll,
             "qz_greedy_step_work_bytes": _ll, "qz_sample_step_work_bytes": _ll,
             "qz_verify_sample_step_work_bytes": _ll, "qz_logits_process_work_bytes": _ll,
-            "qz_logprobs_work_bytes": _ll}
+            "qz_logprobs_work_bytes": _ll, "qz_attention_group_work_floats": _ll}
 
 
 def _load():

@@ -833,12 +833,19 @@ class StreamSession:
 
     decode_rows (None: everything as it was): 17..64 calls integration.set_decode_rows(model, decode_rows),
     so a step of up to that many rows reads every 4-bit weight once on the wide multi-token kernel
-    instead of taking the prefill route; a row's bits are those of the 2..16-row step."""
+    instead of taking the prefill route; a row's bits are those of the 2..16-row step.
+
+    attention_route ("rows": everything as it was): the one-head-per-workgroup attention launches serve up to 8
+    query heads per kv head; a model beyond that (up to 64) runs its step, verify window and prefill windows
+    on layer_ops.attention_group whatever this says.  "group" sends every shape that launch takes to it, on the
+    flat cache only."""
 
     def __init__(self, model, batch: int, max_len: int, *, graph: bool = True, prefill_chunk: Optional[int] = None,
                  kv_pages: Optional[int] = None, prefix_cache: bool = False, kv_dtype: Optional[str] = None,
                  logprobs: Optional[int] = None, prompt_logprobs: bool = False, constraint=None,
-                 logit_bias_slots: int = 0, decode_rows: Optional[int] = None):
+                 logit_bias_slots: int = 0, decode_rows: Optional[int] = None, attention_route: str = "rows"):
+        if attention_route not in ("rows", "group"):
+            raise ValueError(f"StreamSession: attention_route must be 'rows' or 'group', not {attention_route!r}")
         _check_kv_dtype(kv_dtype, "StreamSession", kv_pages)
         _set_decode_rows(model, decode_rows)
         _check_logprobs(logprobs, "StreamSession")
@@ -887,6 +894,11 @@ class StreamSession:
             self._extra = {"_qz_window": (self.window,)}
         else:
             self.cache = StaticCache(config=model.config, max_cache_len=self.max_len)
+        if attention_route == "group":
+            if self._extra:
+                raise ValueError("StreamSession: attention_route='group' serves the flat cache only (no kv_pages, "
+                                 "kv_dtype or sliding-window form of layer_ops.attention_group)")
+            self._extra = {"_qz_route": "group"}
         self._scratch = None   # admit()'s batch-1 StaticCache, made on first use
         self.tok = torch.zeros((batch, 1), dtype=torch.int64, device=dev)
         self.pos = torch.zeros(batch, dtype=torch.int64, device=dev)
@@ -1365,7 +1377,7 @@ class SpeculativeSession(StreamSession):
                  sample: bool = False, prefill_chunk: Optional[int] = None, kv_pages: Optional[int] = None,
                  prefix_cache: bool = False, kv_dtype: Optional[str] = None, logprobs: Optional[int] = None,
                  prompt_logprobs: bool = False, constraint=None, logit_bias_slots: int = 0,
-                 decode_rows: Optional[int] = None):
+                 decode_rows: Optional[int] = None, attention_route: str = "rows"):
         from .core import MT_MAX_TOKENS
 
         if int(draft_tokens) < 1:
@@ -1381,7 +1393,7 @@ class SpeculativeSession(StreamSession):
         super().__init__(model, batch, max_len, graph=graph, prefill_chunk=prefill_chunk, kv_pages=kv_pages,
                          prefix_cache=prefix_cache, kv_dtype=kv_dtype, logprobs=logprobs,
                          prompt_logprobs=prompt_logprobs, constraint=constraint, logit_bias_slots=logit_bias_slots,
-                         decode_rows=decode_rows)
+                         decode_rows=decode_rows, attention_route=attention_route)
         dev = self.device
         self.T, self.ngram, self.sample = T, int(ngram), bool(sample)
         self.tok = torch.zeros((batch, T), dtype=torch.int64, device=dev)

@@ -255,6 +255,7 @@ DECODER_CLASSES = ("LlamaDecoderLayer", "MistralDecoderLayer", "MixtralDecoderLa
 # rotate_half) keep their own code
 ATTENTION_CLASSES = ("LlamaAttention", "MistralAttention", "MixtralAttention", "Qwen2Attention")
 _ROPE_PATCHED = {}  # module name -> original apply_rotary_pos_emb
+GROUP_STEP_CHUNK = 128  # key chunk of layer_ops.attention_group for a step or a verify window: the decode head's
 
 
 def _fused_rmsnorm_forward(mod: nn.Module, orig):
@@ -371,7 +372,14 @@ def _fused_attention_forward(mod: nn.Module, orig):
     `_qz_window` = (W,) (generation.StreamSession on a model with config.sliding_window) goes beside
     `_qz_stream_pos` or `_qz_prefill`: the cache's layer holds rings [B, Hkv, R, D] as keys / values
     (generation.RingKVCache), position p lives in slot p % R and a row sees its last W positions.  The
-    layer runs layer_ops.decode_attention_window / prefill_attention_window -- or raises."""
+    layer runs layer_ops.decode_attention_window / prefill_attention_window -- or raises.
+
+    `_qz_route` ("group", generation's attention_route) goes beside `_qz_stream_pos`, `_qz_verify_pos` or
+    `_qz_prefill` on a flat cache.  Without it each of the three asks its own launch first and
+    layer_ops.attention_group only where that launch refuses (more than 8 query heads per kv head: the group
+    launch takes up to 64), so a model the old launches serve keeps them and their bits; with it every shape
+    the group launch takes goes there.  Key chunk: GROUP_STEP_CHUNK for the step and the verify window, the
+    cache length (one pass, no workspace) for a prefill window."""
     from . import layer_ops
     from .layer_ops import (decode_attention, decode_attention_streams, decode_attention_streams_supported,
                             decode_attention_supported, decode_attention_verify, decode_attention_verify_supported)
@@ -462,7 +470,28 @@ def _fused_attention_forward(mod: nn.Module, orig):
             out = layer_ops.decode_attention_window(q, k, v, cos, sin, keys, values, stream_pos, nq, mod.scaling, W)
         return _project(mod.o_proj, out, residual), None
 
-    def prefill_forward(hidden_states, position_embeddings, past_key_values, spec, residual, kwargs):
+    def group_route(route, old_ok, hidden_states, cos, keys, values, pos, length, nq, key_chunk):
+        """True: the group launch serves this call (asked for, or the old launch refuses and it does not);
+        False: the old launch does; None: neither."""
+        if route is not None and route != "group":
+            raise ValueError(f"_qz_route: {route!r} is not a route (None or 'group')")
+        if route == "group" and layer_ops.attention_group_supported(hidden_states, cos, keys, values, pos, length, nq,
+                                                                    key_chunk):
+            return True
+        if old_ok():
+            return False
+        return True if layer_ops.attention_group_supported(hidden_states, cos, keys, values, pos, length, nq,
+                                                           key_chunk) else None
+
+    def full_lengths(pos, T):
+        """int64 [B] of T on pos's device, made once per (B, T): the len operand of a window whose rows are all real."""
+        memo = mod.__dict__.setdefault("_qz_group_len", {})
+        key = (pos.shape[0], T, pos.device)
+        if key not in memo:
+            memo[key] = torch.full((pos.shape[0],), T, dtype=torch.int64, device=pos.device)
+        return memo[key]
+
+    def prefill_forward(hidden_states, position_embeddings, past_key_values, spec, route, residual, kwargs):
         pos, length, row0 = spec
         layer = None
         if (hidden_states.dim() == 3 and hidden_states.shape[1] >= 1 and position_embeddings is not None
@@ -477,17 +506,25 @@ def _fused_attention_forward(mod: nn.Module, orig):
         keys, values = layer.keys[row0:row0 + nb], layer.values[row0:row0 + nb]
         cos, sin = position_embeddings
         nq = keys.shape[1] * (mod.config.num_attention_heads // mod.config.num_key_value_heads)
-        if not layer_ops.prefill_attention_supported(hidden_states, cos, keys, values, pos, length, nq):
-            raise ValueError("_qz_prefill: prefill_attention does not take these shapes/dtypes/layout")
+        one_pass = -(-keys.shape[2] // layer_ops.PREFILL_TK) * layer_ops.PREFILL_TK
+        group = group_route(route, lambda: layer_ops.prefill_attention_supported(hidden_states, cos, keys, values, pos,
+                                                                                 length, nq),
+                            hidden_states, cos, keys, values, pos, length, nq, one_pass)
+        if group is None:
+            raise ValueError("_qz_prefill: prefill_attention does not take these shapes/dtypes/layout (nor does "
+                             "attention_group)")
         q = mod.q_proj(hidden_states)
         k = mod.k_proj(hidden_states)
         v = mod.v_proj(hidden_states)
         if q.shape[-1] != nq * mod.head_dim or k.shape[-1] != keys.shape[1] * mod.head_dim:
             raise ValueError("_qz_prefill: the projections' widths differ from the cache's heads")
-        out = layer_ops.prefill_attention(q, k, v, cos, sin, keys, values, pos, length, nq, mod.scaling)
+        if group:
+            out = layer_ops.attention_group(q, k, v, cos, sin, keys, values, pos, length, nq, mod.scaling, one_pass)
+        else:
+            out = layer_ops.prefill_attention(q, k, v, cos, sin, keys, values, pos, length, nq, mod.scaling)
         return _project(mod.o_proj, out, residual), None
 
-    def stream_forward(hidden_states, position_embeddings, past_key_values, pos, residual, kwargs):
+    def stream_forward(hidden_states, position_embeddings, past_key_values, pos, route, residual, kwargs):
         layer = None
         if (hidden_states.dim() == 3 and hidden_states.shape[1] == 1 and position_embeddings is not None
                 and not kwargs.get("output_attentions", False) and not mod.training):
@@ -497,17 +534,26 @@ def _fused_attention_forward(mod: nn.Module, orig):
                              "initialised StaticCache layer of this module's head_dim")
         cos, sin = position_embeddings
         nq = layer.keys.shape[1] * (mod.config.num_attention_heads // mod.config.num_key_value_heads)
-        if not decode_attention_streams_supported(hidden_states, cos, layer.keys, layer.values, pos, nq):
-            raise ValueError("_qz_stream_pos: decode_attention_streams does not take these shapes/dtypes/layout")
+        length = full_lengths(pos, 1) if isinstance(pos, torch.Tensor) and pos.dim() == 1 else None
+        group = group_route(route, lambda: decode_attention_streams_supported(hidden_states, cos, layer.keys,
+                                                                              layer.values, pos, nq),
+                            hidden_states, cos, layer.keys, layer.values, pos, length, nq, GROUP_STEP_CHUNK)
+        if group is None:
+            raise ValueError("_qz_stream_pos: decode_attention_streams does not take these shapes/dtypes/layout (nor "
+                             "does attention_group)")
         q = mod.q_proj(hidden_states)
         k = mod.k_proj(hidden_states)
         v = mod.v_proj(hidden_states)
         if q.shape[-1] != nq * mod.head_dim or k.shape[-1] != layer.keys.shape[1] * mod.head_dim:
             raise ValueError("_qz_stream_pos: the projections' widths differ from the cache's heads")
-        out = decode_attention_streams(q, k, v, cos, sin, layer.keys, layer.values, pos, nq, mod.scaling)
+        if group:
+            out = layer_ops.attention_group(q, k, v, cos, sin, layer.keys, layer.values, pos, length, nq, mod.scaling,
+                                            GROUP_STEP_CHUNK)
+        else:
+            out = decode_attention_streams(q, k, v, cos, sin, layer.keys, layer.values, pos, nq, mod.scaling)
         return _project(mod.o_proj, out, residual), None
 
-    def verify_forward(hidden_states, position_embeddings, past_key_values, pos, residual, kwargs):
+    def verify_forward(hidden_states, position_embeddings, past_key_values, pos, route, residual, kwargs):
         layer = None
         if (hidden_states.dim() == 3 and hidden_states.shape[1] >= 2 and position_embeddings is not None
                 and not kwargs.get("output_attentions", False) and not mod.training):
@@ -517,20 +563,32 @@ def _fused_attention_forward(mod: nn.Module, orig):
                              "initialised StaticCache layer of this module's head_dim")
         cos, sin = position_embeddings
         nq = layer.keys.shape[1] * (mod.config.num_attention_heads // mod.config.num_key_value_heads)
-        if not decode_attention_verify_supported(hidden_states, cos, layer.keys, layer.values, pos, nq):
-            raise ValueError("_qz_verify_pos: decode_attention_verify does not take these shapes/dtypes/layout")
+        length = (full_lengths(pos, hidden_states.shape[1]) if isinstance(pos, torch.Tensor) and pos.dim() == 1
+                  else None)
+        group = group_route(route, lambda: decode_attention_verify_supported(hidden_states, cos, layer.keys,
+                                                                             layer.values, pos, nq),
+                            hidden_states, cos, layer.keys, layer.values, pos, length, nq, GROUP_STEP_CHUNK)
+        if group is None:
+            raise ValueError("_qz_verify_pos: decode_attention_verify does not take these shapes/dtypes/layout (nor "
+                             "does attention_group)")
         q = mod.q_proj(hidden_states)
         k = mod.k_proj(hidden_states)
         v = mod.v_proj(hidden_states)
         if q.shape[-1] != nq * mod.head_dim or k.shape[-1] != layer.keys.shape[1] * mod.head_dim:
             raise ValueError("_qz_verify_pos: the projections' widths differ from the cache's heads")
-        out = decode_attention_verify(q, k, v, cos, sin, layer.keys, layer.values, pos, nq, mod.scaling)
+        if group:
+            out = layer_ops.attention_group(q, k, v, cos, sin, layer.keys, layer.values, pos, length, nq, mod.scaling,
+                                            GROUP_STEP_CHUNK)
+        else:
+            out = decode_attention_verify(q, k, v, cos, sin, layer.keys, layer.values, pos, nq, mod.scaling)
         return _project(mod.o_proj, out, residual), None
 
     def forward(hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None,
                 _qz_residual=None, _qz_stream_pos=None, _qz_verify_pos=None, _qz_prefill=None, _qz_paged=None,
-                _qz_window=None, **kwargs):
+                _qz_window=None, _qz_route=None, **kwargs):
         # _qz_residual (the residual-fused decoder layer): return residual + attention output
+        if _qz_route is not None and (_qz_window is not None or _qz_paged is not None):
+            raise ValueError("_qz_route: attention_group serves the flat cache only (no paged, FP8 or ring form)")
         if _qz_window is not None:
             if _qz_paged is not None or _qz_verify_pos is not None:
                 raise ValueError("_qz_window excludes _qz_paged and _qz_verify_pos (no paged ring, no verify window)")
@@ -542,16 +600,16 @@ def _fused_attention_forward(mod: nn.Module, orig):
         if _qz_prefill is not None:
             if _qz_stream_pos is not None or _qz_verify_pos is not None:
                 raise ValueError("_qz_prefill excludes _qz_stream_pos and _qz_verify_pos")
-            return prefill_forward(hidden_states, position_embeddings, past_key_values, _qz_prefill, _qz_residual,
-                                   kwargs)
+            return prefill_forward(hidden_states, position_embeddings, past_key_values, _qz_prefill, _qz_route,
+                                   _qz_residual, kwargs)
         if _qz_verify_pos is not None:   # taken out of kwargs, like _qz_stream_pos below
             if _qz_stream_pos is not None:
                 raise ValueError("_qz_verify_pos and _qz_stream_pos exclude each other")
-            return verify_forward(hidden_states, position_embeddings, past_key_values, _qz_verify_pos, _qz_residual,
-                                  kwargs)
+            return verify_forward(hidden_states, position_embeddings, past_key_values, _qz_verify_pos, _qz_route,
+                                  _qz_residual, kwargs)
         if _qz_stream_pos is not None:   # taken out of kwargs: the original forward never sees it
-            return stream_forward(hidden_states, position_embeddings, past_key_values, _qz_stream_pos, _qz_residual,
-                                  kwargs)
+            return stream_forward(hidden_states, position_embeddings, past_key_values, _qz_stream_pos, _qz_route,
+                                  _qz_residual, kwargs)
         layer = None
         if (hidden_states.dim() == 3 and hidden_states.shape[1] == 1 and position_embeddings is not None
                 and not kwargs.get("output_attentions", False) and not mod.training

@@ -378,6 +378,68 @@ def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: to
     return out
 
 
+GROUP_MAX_G = 64  # query heads per kv head of qz_attention_group (csrc/attn_group.hip: kGroupMaxG)
+
+
+def attention_group_supported(q: torch.Tensor, cos: torch.Tensor, key_cache: torch.Tensor,
+                              value_cache: torch.Tensor, pos, length, num_heads: int, key_chunk) -> bool:
+    """What qz_attention_group takes: prefill_attention_supported's operands with 1 <= Hq/Hkv <= 64 and a
+    key_chunk that is a positive multiple of 64.  Metadata only: nothing is launched or allocated."""
+    if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype in (torch.float16, torch.bfloat16)
+            and q.dim() == 3 and q.shape[1] >= 1) or _needs_grad(q):
+        return False
+    if not (isinstance(key_chunk, int) and not isinstance(key_chunk, bool) and key_chunk > 0
+            and key_chunk % PREFILL_TK == 0):
+        return False
+    if key_cache.dim() != 4 or value_cache.shape != key_cache.shape:
+        return False
+    B, Hkv, L, D = key_cache.shape
+    T = q.shape[1]
+    if (D not in (64, 128) or Hkv == 0 or num_heads % Hkv or not 1 <= num_heads // Hkv <= GROUP_MAX_G
+            or q.shape[0] != B or L == 0 or B > 65535 or num_heads > 65535):
+        return False
+    for t in (key_cache, value_cache):
+        if t.dtype != q.dtype or t.device != q.device or not t.is_contiguous() or t.data_ptr() % 16:
+            return False
+    if not (isinstance(cos, torch.Tensor) and cos.dim() == 3 and cos.shape[0] in (1, B) and cos.shape[1] == T
+            and cos.shape[2] == D and cos.dtype == q.dtype and cos.device == q.device and cos.stride(-1) == 1):
+        return False
+    for p in (pos, length):
+        if not (isinstance(p, torch.Tensor) and p.dtype == torch.int64 and p.dim() == 1 and p.shape[0] == B
+                and p.device == q.device and p.is_contiguous()):
+            return False
+    return True
+
+
+def attention_group(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                    key_cache: torch.Tensor, value_cache: torch.Tensor, pos: torch.Tensor, length: torch.Tensor,
+                    num_heads: int, scale: float, key_chunk: int) -> torch.Tensor:
+    """prefill_attention's window with every query head of a kv head in one MFMA tile, split over keys
+    (qz_attention_group): q [B, T, Hq*D] with T >= 1, k/v [B, T, Hkv*D], cos/sin [B or 1, T, D], pos and
+    length int64 [B], 1 <= Hq/Hkv <= 64.  The cache write, the validity rules and the returned [B, T, Hq*D]
+    are prefill_attention's.  A workgroup takes keys [c*key_chunk, (c+1)*key_chunk); with key_chunk < L the
+    chunks leave fp32 partials in a workspace allocated here and a combine launch merges them.  A row's
+    bits depend on its own q/cos/sin row, its position, cache row b and key_chunk -- not on T, the other
+    streams or length."""
+    if not attention_group_supported(q, cos, key_cache, value_cache, pos, length, num_heads, key_chunk):
+        raise ValueError("attention_group: unsupported shapes/dtypes/layout")
+    B, Hkv, L, D = key_cache.shape
+    T = q.shape[1]
+    _check_window("attention_group", q, k, v, cos, sin, num_heads, D)
+    if k.shape[2] != Hkv * D or v.shape[2] != Hkv * D:
+        raise ValueError("attention_group: k/v width differs from the cache's heads")
+    q2, qs, k2, ks, v2, vs, c2, s2, cs = _prefill_rows(q, k, v, cos, sin, B, T, D)
+    out = torch.empty((B, T, num_heads * D), dtype=q.dtype, device=q.device)
+    nwork = _lib.lib.qz_attention_group_work_floats(B, T, num_heads, Hkv, D, L, key_chunk)
+    work = torch.empty(nwork, dtype=torch.float32, device=q.device) if nwork else None
+    _lib.check(_lib.lib.qz_attention_group(
+        _lib.dtype_code(q.dtype), B, T, num_heads, Hkv, D, L, key_chunk, q2.data_ptr(), qs, k2.data_ptr(), ks,
+        v2.data_ptr(), vs, c2.data_ptr(), s2.data_ptr(), cs, key_cache.data_ptr(), value_cache.data_ptr(),
+        pos.data_ptr(), length.data_ptr(), out.data_ptr(), num_heads * D, _lib.ptr(work), float(scale),
+        _lib.stream_of(q)), "qz_attention_group")
+    return out
+
+
 def ring_size(window: int, chunk: int = 1) -> int:
     """Slots of a ring KV cache for a sliding window of `window` keys when one launch writes up to `chunk`
     new tokens per stream: round_up(window + chunk - 1, 128).  The launch stores its keys before it
